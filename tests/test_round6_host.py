@@ -1,6 +1,7 @@
 """Round 6, host side (no GPU): the CLIPSeg entry point's reference surface — flags, prompts as data, get_prompt — the segmentation data module and its
-shared-memory ring, the metric accumulator, the /dev/shm planning of the loaders, and the oracle's BPE restatement where the reference's merges file is there."""
+shared-memory ring, the metric accumulator, the /dev/shm planning of the loaders, and the oracle's BPE restatement on the reference merge rules it needs (stored as data)."""
 import ast
+import gzip
 import json
 import math
 import os
@@ -10,7 +11,7 @@ import pytest
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
+GOLDEN = os.path.join(ROOT, "tests", "golden")
 
 
 # ------------------------------------------------------------------------------------------------ the CLI is part of the drop-in contract
@@ -47,13 +48,13 @@ def _argparse_table(path):
     return out
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="the reference tree exists in the build container only")
 @pytest.mark.parametrize("entry", ["biomedclip/finetune.py", "biomedclip/segmentation.py", "biomedclip/zero_shot.py", "clipseg/segmentation.py", "metaclip/finetune.py",
                                    "clip/finetune.py", "unimedclip/finetune.py"])
 def test_every_reference_flag_of_every_entry_point_is_there_with_its_default(entry):
     """The argparse tables of reference and build compared syntactically (flag set, default / action / choices expressions); `--device` is the one deliberate
-    difference (decided without a HIP call, src/utils/tools.default_device)."""
-    ref = _argparse_table(os.path.join(REF, "src/models", entry))
+    difference (decided without a HIP call, src/utils/tools.default_device).  The reference's tables are data (tests/golden/reference_cli_tables.json,
+    oracle/gen_host_fixtures.py)."""
+    ref = json.load(open(os.path.join(GOLDEN, "reference_cli_tables.json")))[entry]
     got = _argparse_table(os.path.join(ROOT, "nextgen-uia_amd/src/models", entry))
     assert ref, entry
     for flag, kw in ref.items():
@@ -89,13 +90,23 @@ def test_get_prompt_follows_the_reference_table():
     assert "hash(" not in src and "synthetic_prompt" not in src
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="the merges file is the reference's data and never leaves the build container")
-def test_bpe_restatement_reproduces_the_committed_ids():
+def _merges_file(tmp_path):
+    """A merges file in the reference's format holding the rules of tests/golden/bpe_prompt_case.json at their own lines and an inert filler rule (symbols
+    no byte maps to, so it never matches) at every other line: same ranks, same vocabulary ids for the texts below (oracle/gen_host_fixtures.py)."""
+    from oracle.bpe_ref import N_MERGES
+    rules = json.load(open(os.path.join(GOLDEN, "bpe_prompt_case.json")))["merges"]
+    lines = ["#version: 0.2"] + [" ".join(rules[str(r)]) if str(r) in rules else f"\ue000{r} \ue001" for r in range(N_MERGES)]
+    path = tmp_path / "merges.txt.gz"
+    with gzip.open(path, "wb") as f:
+        f.write("\n".join(lines).encode("utf-8"))
+    return str(path)
+
+
+def test_bpe_restatement_reproduces_the_committed_ids(tmp_path):
     from oracle.bpe_ref import BPE, EOT, SOT
-    from oracle.gen_prompt_ids import prompt_strings
-    bpe = BPE(os.path.join(REF, "src/third_party/openai_clip/bpe_simple_vocab_16e6.txt.gz"))
+    bpe = BPE(_merges_file(tmp_path))
     data = json.load(open(os.path.join(ROOT, "nextgen-uia_amd/src/models/clipseg/prompt_ids.json")))
-    for name, text in prompt_strings().items():
+    for name, text in json.load(open(os.path.join(GOLDEN, "bpe_prompt_case.json")))["prompts"].items():
         assert bpe.tokenize(text) == data["prompts"][name]["ids"], name
     assert bpe.tokenize("a photo of a cat") == [SOT, 320, 1125, 539, 320, 2368, EOT] + [0] * 70         # the well-known CLIP example
     with pytest.raises(RuntimeError):
@@ -294,7 +305,7 @@ def test_bench_help_and_telemetry_without_a_gpu():
     import subprocess
     import sys
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and "--gpus" in r.stdout and "--steps" in r.stdout and "--warmup" in r.stdout, r.stderr[-500:]
+    assert r.returncode == 0 and "--gpus" in r.stdout and "--steps" in r.stdout and "--warmup" in r.stdout and "--dump-outputs" in r.stdout, r.stderr[-500:]
     from uia_hip.telemetry import PowerSampler
 
     class _NoDevice:
@@ -305,3 +316,17 @@ def test_bench_help_and_telemetry_without_a_gpu():
     s = PowerSampler(_NoDevice, "cuda:0")
     s.start()
     assert s.stop() is None
+
+
+def test_bench_dump_outputs_writes_npy_files_within_64_mb(tmp_path):
+    """bench.py --dump-outputs: one DIR/<name>.npy per captured array, dtype and values as captured; more than 64 MB in all is refused."""
+    import bench
+    arrays = {"loss": np.array([1.25], dtype=np.float64), "params": np.arange(12, dtype=np.float32).reshape(3, 4)}
+    bench.dump_outputs(arrays, str(tmp_path / "out"))
+    assert sorted(os.listdir(tmp_path / "out")) == ["loss.npy", "params.npy"]
+    for k, a in arrays.items():
+        got = np.load(tmp_path / "out" / (k + ".npy"))
+        assert got.dtype == a.dtype and np.array_equal(got, a)
+    with pytest.raises(AssertionError):
+        bench.dump_outputs({"big": np.zeros((64 << 20) // 4 + 1, dtype=np.float32)}, str(tmp_path / "big"))
+    assert not (tmp_path / "big").exists()

@@ -1,5 +1,5 @@
 import sys, os, math, json
-ROOT=os.environ.get("GRAFT_REPO_ROOT", "/root/repo")
+ROOT=os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0]=[ROOT, os.path.join(ROOT,"nextgen-uia_amd"), os.path.join(ROOT,"tools")]
 import descent_check as D
 for rep in range(3):
