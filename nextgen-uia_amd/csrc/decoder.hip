@@ -372,6 +372,12 @@ int uia_attn_small_launch(hipStream_t stream, int dtype, const UiaAttnParams& p,
     UIA_CHECK_ARG(p.dh == 16 || p.dh == 32, "uia_attn: head dim %d unsupported (16, 32 or 64)", p.dh);
     UIA_CHECK_ARG(!p.cu_seqlens, "uia_attn: packed sequences (cu_seqlens) need head dim 64");
     UIA_CHECK_ARG(p.L > 0 && p.L <= 1024 && p.B > 0 && p.H > 0, "uia_attn: bad shape");
+    // the same operand contract as the head-dim-64 launchers: a key-padding mask without keylen is refused, not run unmasked,
+    // and a backward without lse / dout / gradients fails here instead of dereferencing null on the device
+    UIA_CHECK_ARG(p.q && p.k && p.v && p.out, "uia_attn: null tensor");
+    UIA_CHECK_ARG(p.mask_kind >= UIA_MASK_NONE && p.mask_kind <= UIA_MASK_KEYPAD, "uia_attn: bad mask kind");
+    UIA_CHECK_ARG(p.mask_kind != UIA_MASK_KEYPAD || p.keylen, "uia_attn: key-padding mask needs keylen");
+    UIA_CHECK_ARG(!bwd || (p.dout && p.lse && p.dq && p.dk && p.dv), "uia_attn_bwd: null tensor");
     {   // bf16, head dim 16, no mask: the MFMA kernels (attention_dh16.hip).  UIA_ATTN_DH16=0 keeps the scalar kernels below (A/B runs, parity cross-check).
         static const bool mfma = []() { const char* e = getenv("UIA_ATTN_DH16"); return !(e && e[0] == '0'); }();
         if (mfma && uia_attn_dh16_ok(dtype, p)) return uia_attn_dh16_launch(stream, p, bwd);
