@@ -391,6 +391,20 @@ int uia_segment_mean_bwd(void* stream, int B, int n, int C, const float* dout, f
 size_t uia_dicece_workspace_bytes(int B);
 int uia_dicece_fwd_bwd(void* stream, int B, int C, int HW, const float* logits, const float* label, float smooth_nr, float smooth_dr,
                        float* ws, float* loss, float* dlogits);
+/* MONAI FocalLoss(to_onehot_y=True) in its sigmoid form, mean reduction, of the classification entry points (reference
+ * src/models/biomedclip/classification.py:77): loss (one float, the mean over all N*C elements) and d loss / d logits in one call.
+ * logits, dlogits fp32 [N,C]; labels int64 [N], target one_hot(label); 2 <= C <= 64, 1 <= N <= 2^20; gamma >= 0; alpha < 0 means none,
+ * else the element weight is t*alpha + (1-t)*(1-alpha).  A label outside [0, C) makes the loss (and its row of dlogits) NaN; it is never an index.
+ * Deterministic (fixed-order two-stage sum in fp64, no atomics).  ws: uia_focal_workspace_bytes(N, C) of scratch. */
+size_t uia_focal_workspace_bytes(int N, int C);
+int uia_focal_fwd_bwd(void* stream, int N, int C, const float* logits, const int64_t* labels, float gamma, float alpha, void* ws, size_t ws_bytes,
+                      float* loss, float* dlogits);
+/* Binary classification counts and AUROC of a split (torchmetrics Accuracy / Precision / Recall / F1Score / AUROC, task="binary").
+ * p1 fp32 [N] (probability of class 1), labels int64 [N] in {0,1}, perm int64 [N]: the permutation that sorts p1 ascending; 1 <= N <= 2^24.
+ * record fp64 [5]: TP, FP, TN, FN at p1 > 0.5 (strict) and the exact tie-aware AUROC (ties count 1/2 = the trapezoidal ROC area; 0.0 when a
+ * class is absent).  A label outside {0,1} or a perm entry outside [0,N) makes every field NaN.  ws: uia_binary_cls_stats_workspace_bytes(N). */
+size_t uia_binary_cls_stats_workspace_bytes(int N);
+int uia_binary_cls_stats(void* stream, int N, const float* p1, const int64_t* labels, const int64_t* perm, void* ws, size_t ws_bytes, double* record);
 
 /* ---------------------------------------------------------------------------------------------
  * Layout helpers around the GEMMs. */

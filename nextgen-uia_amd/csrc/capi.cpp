@@ -193,6 +193,16 @@ int uia_dicece_fwd_bwd(void* stream, int B, int C, int HW, const float* logits, 
     return uia_dicece_launch((hipStream_t)stream, B, C, HW, logits, label, smooth_nr, smooth_dr, ws, loss, dlogits);
 }
 
+size_t uia_focal_workspace_bytes(int N, int C) { return uia_focal_ws_bytes(N, C); }
+int uia_focal_fwd_bwd(void* stream, int N, int C, const float* logits, const int64_t* labels, float gamma, float alpha, void* ws, size_t ws_bytes,
+                      float* loss, float* dlogits) {
+    return uia_focal_launch((hipStream_t)stream, N, C, logits, labels, gamma, alpha, ws, ws_bytes, loss, dlogits);
+}
+size_t uia_binary_cls_stats_workspace_bytes(int N) { return uia_binary_cls_stats_ws_bytes(N); }
+int uia_binary_cls_stats(void* stream, int N, const float* p1, const int64_t* labels, const int64_t* perm, void* ws, size_t ws_bytes, double* record) {
+    return uia_binary_cls_stats_launch((hipStream_t)stream, N, p1, labels, perm, ws, ws_bytes, record);
+}
+
 int uia_im2col_padded(void* stream, int dtype, int B, int C, int H, int W, int P, const float* img, void* cols, int64_t ldo) {
     return uia_im2col_padded_launch((hipStream_t)stream, dtype, B, C, H, W, P, img, cols, (long)ldo);
 }

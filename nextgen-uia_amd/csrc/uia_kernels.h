@@ -72,6 +72,12 @@ int uia_upsample_bilinear_launch(hipStream_t stream, bool bwd, int B, int C, int
 int uia_segment_mean_launch(hipStream_t stream, bool bwd, int B, int n, int C, const float* in, float* out, long ld);
 size_t uia_dicece_ws_floats(int B);
 int uia_dicece_launch(hipStream_t stream, int B, int C, int HW, const float* logits, const float* label, float nr, float dr, float* ws, float* loss, float* dlogits);
+size_t uia_focal_ws_bytes(int N, int C);
+int uia_focal_launch(hipStream_t stream, int N, int C, const float* logits, const int64_t* labels, float gamma, float alpha, void* ws, size_t ws_bytes,
+                     float* loss, float* dlogits);
+size_t uia_binary_cls_stats_ws_bytes(int N);
+int uia_binary_cls_stats_launch(hipStream_t stream, int N, const float* p1, const int64_t* labels, const int64_t* perm, void* ws, size_t ws_bytes,
+                                double* record);
 int uia_im2col_padded_launch(hipStream_t stream, int dtype, int B, int C, int H, int W, int P, const float* img, void* out, long ldo);
 int uia_embed_bwd_launch(hipStream_t stream, int rows, int D, int vocab, const int64_t* ids, const float* dx, float* dtable, long pad_id);
 int uia_embed_packed_launch(hipStream_t stream, int rows, int D, int vocab, int max_pos, const int64_t* ids, const int64_t* pos_idx, const float* table, const float* pos, const float* type0, float* out);

@@ -1,0 +1,88 @@
+"""Image / label data for the classification entry points (counterpart of the reference's src/datasets/classification.py).
+
+The reference reads grayscale PNGs listed in ../data/NextGen-UIA/classification/<dataset>/{train,val,test}.txt with labels from labels.csv, augments them
+with PIL / torchvision (:14-147) and hands batches of (image float32 [B, 3, S, S] in [0, 1] — ONE grayscale channel repeated, :183, :201-203 — label int64 [B],
+file names) to the loop, `shuffle=True, drop_last=True` for training and neither for validation / test (:232-262).  PIL / torchvision I/O and augmentation are
+host-side work outside the hot path (and absent from the build image); what the hot path needs is that batch contract and the three splits.
+
+`--synthetic` supplies them deterministically by seed and balanced (even indices class 0, odd indices class 1): every image is U[0,1) texture scaled by 0.6;
+a class-1 image also carries a bright axis-aligned ellipse (the synthetic lesion of src/datasets/segmentation.py), so the classes are learnable.
+`--data_pt` takes real data as a .pt file of {"images": uint8 [N, 1 or 3, S, S], "labels": [N], optional "names", optional "split": {"train": idx,
+"val": idx, "test": idx}} — without "split", 70 / 10 / 20 in file order.
+
+A split lives in memory as tensors and a batch is an index gather, so loading runs in this process; a batch travels host -> device as ONE channel
+(float32, the towers' patch embedding takes it with the channel-summed kernel, uia_hip.functional.gray_conv_weight) plus its int64 labels through
+engine.DevicePrefetcher (`second=second_of`)."""
+import torch
+from torch.utils.data import DataLoader, Dataset
+
+
+def synthetic_split(n, size, seed):
+    """(images float32 [n, 1, S, S] in [0, 1], labels int64 [n]): labels alternate 0, 1; class 1 carries an ellipse of brightness 0.9 + texture·0.1."""
+    g = torch.Generator().manual_seed(seed)
+    img = torch.rand(n, 1, size, size, generator=g) * 0.6
+    labels = torch.arange(n, dtype=torch.int64) % 2
+    c = torch.rand(n, 2, generator=g) * size * 0.5 + size * 0.25
+    r = torch.rand(n, 2, generator=g) * size * 0.15 + size * 0.12
+    yy, xx = torch.meshgrid(torch.arange(size, dtype=torch.float32), torch.arange(size, dtype=torch.float32), indexing="ij")
+    inside = (((yy[None] - c[:, 0, None, None]) / r[:, 0, None, None]) ** 2 + ((xx[None] - c[:, 1, None, None]) / r[:, 1, None, None]) ** 2) <= 1
+    lesion = inside & (labels[:, None, None] == 1)
+    img[:, 0] = torch.where(lesion, 0.9 + img[:, 0] / 6, img[:, 0])
+    return img, labels
+
+
+class TensorClassification(Dataset):
+    def __init__(self, images, labels, names):
+        self.images, self.labels, self.names = images, labels, names
+
+    def __len__(self):
+        return len(self.names)
+
+    def __getitem__(self, i):
+        img = self.images[i]
+        img = img.float() / 255.0 if img.dtype == torch.uint8 else img.float()
+        return img[:1], self.labels[i], self.names[i]          # the reference converts every image to one grayscale channel (:180)
+
+
+def _collate(samples):
+    return torch.stack([s[0] for s in samples]), torch.stack([s[1] for s in samples]).to(torch.int64), [s[2] for s in samples]
+
+
+def second_of(batch):
+    """What engine.DevicePrefetcher copies beside the images: the labels."""
+    return batch[1]
+
+
+class DataModule:
+    def __init__(self, args):
+        self.args = args
+        if getattr(args, "data_pt", None):
+            blob = torch.load(args.data_pt)
+            n = len(blob["images"])
+            names = list(blob.get("names") or [f"{i:05d}.png" for i in range(n)])
+            labels = torch.as_tensor(blob["labels"]).reshape(n).to(torch.int64)
+            split = blob.get("split")
+            if split is None:                                   # 70 / 10 / 20 in file order (the reference's lists are pre-shuffled text files)
+                a, b = int(n * 0.7), int(n * 0.8)
+                split = {"train": list(range(a)), "val": list(range(a, b)), "test": list(range(b, n))}
+            mk = lambda idx: TensorClassification(blob["images"][list(idx)], labels[list(idx)], [names[i] for i in idx])
+            self.train_dataset, self.val_dataset, self.test_dataset = mk(split["train"]), mk(split["val"]), mk(split["test"])
+        elif getattr(args, "synthetic", False):
+            mk = lambda n, seed, prefix: TensorClassification(*synthetic_split(n, args.img_size, seed), [f"{prefix}_{i:05d}.png" for i in range(n)])
+            self.train_dataset = mk(args.synthetic_train, args.seed, "train")
+            self.val_dataset = mk(args.synthetic_val, args.seed + 1, "val")
+            self.test_dataset = mk(args.synthetic_test, args.seed + 2, "test")
+        else:
+            raise RuntimeError("no dataset: pass --synthetic or --data_pt (the reference's PIL/torchvision loaders read ../data/NextGen-UIA and are outside this build)")
+
+    def _loader(self, ds, train):
+        return DataLoader(ds, batch_size=self.args.batch_size, shuffle=train, drop_last=train, num_workers=0, collate_fn=_collate)
+
+    def train_dataloader(self):
+        return self._loader(self.train_dataset, True)
+
+    def val_dataloader(self):
+        return self._loader(self.val_dataset, False)
+
+    def test_dataloader(self):
+        return self._loader(self.test_dataset, False)

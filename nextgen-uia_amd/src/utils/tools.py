@@ -118,25 +118,29 @@ def report_test(args, stats, saved_best, rank=0):
     """The tail of the segmentation entry points' test() (reference src/models/clipseg/segmentation.py:275-306, biomedclip/segmentation.py:322-353): the
     Metric / Mean / Std table (Dice and IoU in percent) to the log, then runs/<exp>/<dataset>/test/<time>_iou=<iou>/ with results.csv
     (DataFrame.to_csv(index=False, float_format="%.2f"): NaN as an empty field), a copy of the checkpoint, the viz folder and the log."""
-    import datetime
-    import shutil
     rows = [("Dice", stats["dice_mean"] * 100, stats["dice_std"] * 100), ("IoU", stats["iou_mean"] * 100, stats["iou_std"] * 100),
             ("HD95", stats["hd95_mean"], stats["hd95_std"]), ("ASD", stats["asd_mean"], stats["asd_std"])]
     table = f"{'Metric':>6} {'Mean':>6} {'Std':>6}\n" + "".join(f"{m:>6} {a:6.2f} {s_:6.2f}\n" for m, a, s_ in rows)
     logging.info(f"\n{'=' * 50}\n" + table + f"{'=' * 50}\n")
     if rank != 0:
         return None
-    backup_folder = os.path.join(args.test_snapshot_path, f"{datetime.datetime.now().strftime('%Y_%m_%d_%H_%M_%S')}_iou={stats['iou_mean'] * 100:.2f}")
+    lines = ["Metric,Mean,Std"] + [f"{m},{'' if a != a else '%.2f' % a},{'' if s_ != s_ else '%.2f' % s_}" for m, a, s_ in rows]
+    return backup_test_run(args, f"iou={stats['iou_mean'] * 100:.2f}", lines, saved_best)
+
+
+def backup_test_run(args, tag, csv_lines, saved_best):
+    """runs/<exp>/<dataset>/test/<time>_<tag>/ with results.csv (the given lines), a copy of the checkpoint, the viz folder and the log; returns the csv path."""
+    import datetime
+    import shutil
+    backup_folder = os.path.join(args.test_snapshot_path, f"{datetime.datetime.now().strftime('%Y_%m_%d_%H_%M_%S')}_{tag}")
     base, n = backup_folder, 1
-    while os.path.exists(backup_folder):                        # two tests within one second with the same IoU (the reference's os.makedirs raises there)
+    while os.path.exists(backup_folder):                        # two tests within one second with the same tag (the reference's os.makedirs raises there)
         n += 1
         backup_folder = f"{base}__{n}"
     os.makedirs(backup_folder)
     csv_path = os.path.join(backup_folder, "results.csv")
     with open(csv_path, "w") as f:
-        f.write("Metric,Mean,Std\n")
-        for m, a, s_ in rows:
-            f.write(f"{m},{'' if a != a else '%.2f' % a},{'' if s_ != s_ else '%.2f' % s_}\n")
+        f.write("".join(line + "\n" for line in csv_lines))
     logging.info(f"Results saved to: {csv_path}")
     shutil.copy(saved_best, os.path.join(backup_folder, "best_model.pth"))
     viz_path = args.test_snapshot_path + "/viz"

@@ -1384,3 +1384,31 @@ def dicece_fwd_bwd(logits, label, smooth_nr=1e-8, smooth_dr=1e-8):
     dl = torch.empty_like(logits)
     check(lib().uia_dicece_fwd_bwd(_stream(), B, Cc, H * W, _p(logits), _p(lab), smooth_nr, smooth_dr, _p(ws), _p(loss), _p(dl)), "uia_dicece_fwd_bwd")
     return loss, dl
+
+
+def focal_fwd_bwd(logits, labels, gamma=2.0, alpha=None):
+    """logits fp32 [N,C], labels int64 [N] -> (loss 0-dim fp32 = mean over N·C of MONAI's sigmoid focal term, dlogits fp32 [N,C] = d loss / d logits).
+    alpha None: no class weighting.  A label outside [0, C) makes the loss NaN."""
+    assert logits.dtype == torch.float32 and logits.is_contiguous() and logits.dim() == 2
+    N, Cc = logits.shape
+    lab = labels.reshape(N).to(torch.int64).contiguous()
+    ws = torch.empty(lib().uia_focal_workspace_bytes(N, Cc), device=logits.device, dtype=torch.uint8)
+    loss = torch.empty((), device=logits.device, dtype=torch.float32)
+    dl = torch.empty_like(logits)
+    check(lib().uia_focal_fwd_bwd(_stream(), N, Cc, _p(logits), _p(lab), float(gamma), -1.0 if alpha is None else float(alpha), _p(ws), ws.numel(),
+                                  _p(loss), _p(dl)), "uia_focal_fwd_bwd")
+    return loss, dl
+
+
+def binary_cls_stats(p1, labels):
+    """p1 fp32 [N] (probability of class 1), labels int64 [N] in {0, 1} -> fp64 device record [5]: TP, FP, TN, FN at p1 > 0.5 and the tie-aware AUROC.
+    The sort is plumbing (torch.sort on the device); the grouped rank sum and the counts are the kernel's."""
+    p1 = p1.reshape(-1).to(torch.float32).contiguous()
+    lab = labels.reshape(-1).to(torch.int64).contiguous()
+    assert p1.numel() == lab.numel() and p1.device == lab.device
+    perm = torch.sort(p1, stable=True).indices
+    N = p1.numel()
+    ws = torch.empty(lib().uia_binary_cls_stats_workspace_bytes(N), device=p1.device, dtype=torch.uint8)
+    rec = torch.empty(5, device=p1.device, dtype=torch.float64)
+    check(lib().uia_binary_cls_stats(_stream(), N, _p(p1), _p(lab), _p(perm), _p(ws), ws.numel(), _p(rec)), "uia_binary_cls_stats")
+    return rec
