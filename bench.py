@@ -12,6 +12,12 @@ flat adapter-gradient buffer (1.34 M fp32) is all-reduced once per step with RCC
 12 blocks each followed by a Mona adapter) + encode_text (frozen BERT-base, dense L = 256, no padded-token skipping) +
 InfoNCE + backward through blocks 11..1 and all 12 adapters + gradient clipping + AdamW.  Inputs are resident in HBM
 before the timed region.  Prints ONE JSON line on rank 0.
+
+A plain run does only what the headline needs: set up, warm up, time --steps, write --dump-outputs, print the line.  Everything
+else the benchmark measures (the entry-point child processes, the secondary lines, `other_forms`, the CPU baseline, the per-kernel
+roofline from extra profiled steps) runs with --full:
+
+    python bench.py --full
 """
 import argparse
 import contextlib
@@ -35,7 +41,7 @@ PEAK_BF16_TFLOPS = 2500.0          # MI355X dense bf16 MFMA (MI355X_MICROARCH.md
 TRAFFIC_FILE = "r06_traffic_pmc.json"   # tools/pmc_traffic.sh on the tree that is benchmarked; tests/test_host_logic.py checks that every instantiation is in it
 
 
-def parse():
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=8)
@@ -46,6 +52,9 @@ def parse():
     ap.add_argument("--batch", type=int, default=0, help="samples per GPU (default: 256 for mona, 128 for the secondary configs)")
     ap.add_argument("--variant", default="freq_enhanced", help="Mona variant (reference default: biomedclip/finetune.py:76)")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
+    ap.add_argument("--full", action="store_true", help="also measure everything beyond the headline figure: the entry-point child processes, the secondary lines, "
+                    "`other_forms`, the CPU baseline and the per-kernel `roofline` (one or two extra profiled steps after the timed region).  The --no-* options "
+                    "below leave parts of it out.  Without --full those fields are null or absent")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--overlap-text", action="store_true", help=argparse.SUPPRESS)           # the default since round 4 (kept so that old command lines still parse)
     ap.add_argument("--no-overlap-text", action="store_true", help="run the frozen text tower on the image tower's stream.  Default (round 4): on a second HIP "
@@ -55,8 +64,8 @@ def parse():
                     "one update per batch) run as a child process after the timed region, its steady-state ms per update printed beside the headline")
     ap.add_argument("--entry-steps", type=int, default=60, help="updates per epoch of the entry-point run (3 epochs; the first is warm-up)")
     ap.add_argument("--no-secondary", action="store_true", help="skip the two secondary lines (BASELINE configs[3] and the per-GPU shape of configs[4], 15 steps each, "
-                    "no CPU leg) that the default single-GPU run prints under `secondary`")
-    ap.add_argument("--also-streams", type=int, default=1, help="after the timed region, time 5 more steps each of two other forms of the step (everything on one stream; the text tower on "
+                    "no CPU leg) that a single-GPU --full run prints under `secondary`")
+    ap.add_argument("--also-streams", type=int, default=1, help="with --full, after the timed region, time 5 more steps each of two other forms of the step (everything on one stream; the text tower on "
                     "valid tokens only) and report them beside the headline as `other_forms` (0 = skip)")
     ap.add_argument("--streams", type=int, default=1, help="cut each rank's batch into this many slices whose towers run on as many HIP streams (same batch, "
                     "same single InfoNCE over all pairs, same gradients: engine.contrastive_step(streams=...))")
@@ -115,7 +124,12 @@ def parse():
                     "the reference-equivalent local loss; changes the objective, not the headline configuration")
     ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write what the last timed step handed its caller (loss, updated "
                     "trainable parameters) as DIR/<name>.npy (float32 / float64); inputs are seeded, so two builds can be compared output for output")
-    return ap.parse_args()
+    args = ap.parse_args(argv)
+    if not args.full:
+        # a plain run: the headline figure only (set-up, warm-up, the timed steps, --dump-outputs, the line); the rest is --full's
+        args.no_entry_point = args.no_secondary = args.no_cpu_baseline = True
+        args.also_streams = 0
+    return args
 
 
 def synthetic_batch(batch, rank, device):
@@ -352,7 +366,7 @@ def dump_outputs(arrays, path):
 
 def timed_loop(step, args, world, device, ops, torch, outputs=None):
     """W untimed warm-up steps, then EXACTLY K steps bracketed by barrier + synchronize; returns (seconds MAX over ranks, per-rank list,
-    last loss, events of one extra profiled step [, of a serialised one]).  With --dump-outputs, `outputs()` (name -> device tensor) and the
+    last loss, events of one extra profiled step [, of a serialised one] with --full, else empty).  With --dump-outputs, `outputs()` (name -> device tensor) and the
     last loss are copied to the host into OUTPUTS[args.config] before any further step runs."""
     def barrier():
         if world > 1:
@@ -377,19 +391,21 @@ def timed_loop(step, args, world, device, ops, torch, outputs=None):
     if getattr(args, "dump_outputs", "") and outputs is not None:
         OUTPUTS[args.config] = {"loss": torch.as_tensor(loss).detach().reshape(1).to("cpu", torch.float64).numpy(),
                                 **{k: v.detach().to("cpu", torch.float32).numpy().copy() for k, v in outputs().items()}}
-    # per-launch HIP events (on the launch stream) around every uia_gemm of ONE more step of the same loop, outside the timed region:
-    # the event records cost host time the throughput figure should not carry; the step itself is identical to the timed ones
-    ops.GEMM_PROFILE = []
-    step(mode)
-    torch.cuda.synchronize()
-    prof, ops.GEMM_PROFILE = ops.GEMM_PROFILE, None
-    prof_serial = prof
-    if multi:
-        # one extra, untimed step with the two towers serialised on one stream: the kernels' rates without the other stream beside them
+    prof = prof_serial = []                 # no events: gemm_roofline() returns None (a plain run has no `roofline`)
+    if args.full:
+        # per-launch HIP events (on the launch stream) around every uia_gemm of ONE more step of the same loop, outside the timed region:
+        # the event records cost host time the throughput figure should not carry; the step itself is identical to the timed ones
         ops.GEMM_PROFILE = []
-        step(False)
+        step(mode)
         torch.cuda.synchronize()
-        prof_serial, ops.GEMM_PROFILE = ops.GEMM_PROFILE, None
+        prof, ops.GEMM_PROFILE = ops.GEMM_PROFILE, None
+        prof_serial = prof
+        if multi:
+            # one extra, untimed step with the two towers serialised on one stream: the kernels' rates without the other stream beside them
+            ops.GEMM_PROFILE = []
+            step(False)
+            torch.cuda.synchronize()
+            prof_serial, ops.GEMM_PROFILE = ops.GEMM_PROFILE, None
     per_rank = [elapsed]
     if world > 1:
         t = torch.zeros(world, device=device, dtype=torch.float64)
@@ -494,6 +510,7 @@ def main():
         os._exit(13)
     if rank == 0:
         out["power"] = POWER.get(args.config)                # rank 0's GPU during the timed steps (None where the driver's hwmon files are not readable)
+        out["full"] = args.full
     if rank == 0 and world == 1 and args.config == "mona" and not args.no_secondary:
         out["secondary"] = secondary_lines(args, device)
     if rank == 0 and args.dump_outputs:

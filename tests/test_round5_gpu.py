@@ -233,14 +233,14 @@ def test_finetune_cli_as_a_child_process_with_loader_workers(tmp_path):
 def test_bench_under_torchrun_with_one_rank(tmp_path):
     """The driver's multi-GPU command line at N = 1: `python -m torch.distributed.run --nproc-per-node 1 ... bench.py --gpus 1` (launcher started as a child process).
     stdout is ONE JSON line (RCCL's banner and the injector's go to stderr), the line says that the RCCL communicator existed and had one rank — the N = 1 step
-    already runs uia_allreduce_sum — and carries the contract's keys."""
+    already runs uia_allreduce_sum — and carries the contract's keys (with --full: the roofline too)."""
     import json
     import os
     import subprocess
     import sys
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1", "--master-port", str(29500 + os.getpid() % 400),
-           os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-secondary", "--also-streams", "0", "--no-entry-point"]
+           os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-secondary", "--also-streams", "0", "--no-entry-point"]
     r = subprocess.run(cmd, cwd=tmp_path, capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]

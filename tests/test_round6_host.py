@@ -330,3 +330,32 @@ def test_bench_dump_outputs_writes_npy_files_within_64_mb(tmp_path):
     with pytest.raises(AssertionError):
         bench.dump_outputs({"big": np.zeros((64 << 20) // 4 + 1, dtype=np.float32)}, str(tmp_path / "big"))
     assert not (tmp_path / "big").exists()
+
+
+def test_bench_plain_run_times_the_steps_only_and_full_adds_the_rest():
+    """A plain `bench.py` run is set-up, warm-up, the timed steps and the line: no entry-point children, secondary lines, other forms, CPU baseline or
+    profiled extra steps (so no roofline).  --full runs all of them, and the --no-* options still leave parts of it out."""
+    import types
+    import bench
+    plain, full = bench.parse(["--steps", "3", "--warmup", "2"]), bench.parse(["--full"])
+    assert not plain.full and plain.no_entry_point and plain.no_secondary and plain.no_cpu_baseline and plain.also_streams == 0
+    assert full.full and not (full.no_entry_point or full.no_secondary or full.no_cpu_baseline) and full.also_streams == 1
+    assert bench.parse(["--full", "--no-secondary"]).no_secondary
+
+    class _Torch:
+        class cuda:
+            @staticmethod
+            def synchronize():
+                pass
+
+            @staticmethod
+            def get_device_properties(d):
+                raise RuntimeError("no GPU")
+
+    for args, extra in ((plain, []), (full, [True, False])):
+        modes, ops = [], types.SimpleNamespace(GEMM_PROFILE=None)
+        args.overlap_text = True                                     # two streams: --full adds one profiled step as timed and one serialised step
+        _, _, loss, prof, prof_serial = bench.timed_loop(lambda m: modes.append(m) or 0.5, args, 1, "cuda:0", ops, _Torch)
+        assert modes == [True] * (args.warmup + args.steps) + extra and loss == 0.5 and ops.GEMM_PROFILE is None
+        if not args.full:
+            assert prof == [] and prof_serial == [] and bench.gemm_roofline(prof, prof_serial, args, 40.0, ops, torch) is None

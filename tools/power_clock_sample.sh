@@ -7,7 +7,7 @@ cd $GRAFT_REPO_ROOT
 rocm-smi --showmaxpower --showpower --showclocks --showperflevel > $out/idle.txt 2>&1
 ( while true; do date +%s.%N; rocm-smi --showpower --showclocks 2>/dev/null | grep -E "Power|sclk|mclk|fclk"; sleep 0.5; done ) > $out/samples.txt 2>&1 &
 S=$!
-python bench.py --steps 150 --warmup 5 --no-cpu-baseline --no-secondary --no-entry-point --also-streams 0 > $out/bench.json 2> $out/bench.err
+python bench.py --full --steps 150 --warmup 5 --no-cpu-baseline --no-secondary --no-entry-point --also-streams 0 > $out/bench.json 2> $out/bench.err
 kill $S
 python - "$out" <<'PY'
 import re, sys, json
