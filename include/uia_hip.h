@@ -405,6 +405,17 @@ int uia_focal_fwd_bwd(void* stream, int N, int C, const float* logits, const int
  * class is absent).  A label outside {0,1} or a perm entry outside [0,N) makes every field NaN.  ws: uia_binary_cls_stats_workspace_bytes(N). */
 size_t uia_binary_cls_stats_workspace_bytes(int N);
 int uia_binary_cls_stats(void* stream, int N, const float* p1, const int64_t* labels, const int64_t* perm, void* ws, size_t ws_bytes, double* record);
+/* Surface-distance metrics of the segmentation MetricAccumulator (reference src/utils/tools.py:185-206: MONAI 1.5.1 compute_hausdorff_distance(
+ * include_background=False, percentile=95) and compute_average_surface_distance(include_background=False, symmetric=False), spacing=None).
+ * logits fp32 [B,2,H,W], label fp32 [B,1,H,W]; 1 <= H, W <= 1024, B >= 1.  Per image: P = argmax(logits) == 1 (tie -> class 0, NaN is the maximum),
+ * G = label > 0, edges E(M) = M & ~erode(M) (4-neighbour, out of image = background), d(A->B) = float32 exact Euclidean pixel distance from each
+ * pixel of E(A) to the nearest pixel of E(B).  hd[b] = max(q(d(P->G)), q(d(G->P))) with q = torch.quantile(d, percentile / 100) (0 <= percentile
+ * <= 100; percentile 0 is the maximum, as in MONAI), asd[b] = mean of d(P->G); both fp64, NaN when P or G is empty.  Unit spacing in both axes: a
+ * physical spacing would scale the two axes of the integer squared distance.  Deterministic (integer selection, fixed-order fp64 sums, no float
+ * atomics).  ws: uia_surface_distances_workspace_bytes(B, H, W) of scratch (about 14 bytes per pixel). */
+size_t uia_surface_distances_workspace_bytes(int B, int H, int W);
+int uia_surface_distances(void* stream, int B, int H, int W, const float* logits, const float* label, float percentile, void* ws, size_t ws_bytes,
+                          double* hd, double* asd);
 
 /* ---------------------------------------------------------------------------------------------
  * Layout helpers around the GEMMs. */

@@ -203,6 +203,12 @@ int uia_binary_cls_stats(void* stream, int N, const float* p1, const int64_t* la
     return uia_binary_cls_stats_launch((hipStream_t)stream, N, p1, labels, perm, ws, ws_bytes, record);
 }
 
+size_t uia_surface_distances_workspace_bytes(int B, int H, int W) { return uia_surface_ws_bytes(B, H, W); }
+int uia_surface_distances(void* stream, int B, int H, int W, const float* logits, const float* label, float percentile, void* ws, size_t ws_bytes,
+                          double* hd, double* asd) {
+    return uia_surface_launch((hipStream_t)stream, B, H, W, logits, label, percentile, ws, ws_bytes, hd, asd);
+}
+
 int uia_im2col_padded(void* stream, int dtype, int B, int C, int H, int W, int P, const float* img, void* cols, int64_t ldo) {
     return uia_im2col_padded_launch((hipStream_t)stream, dtype, B, C, H, W, P, img, cols, (long)ldo);
 }

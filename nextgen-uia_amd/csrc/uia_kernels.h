@@ -78,6 +78,9 @@ int uia_focal_launch(hipStream_t stream, int N, int C, const float* logits, cons
 size_t uia_binary_cls_stats_ws_bytes(int N);
 int uia_binary_cls_stats_launch(hipStream_t stream, int N, const float* p1, const int64_t* labels, const int64_t* perm, void* ws, size_t ws_bytes,
                                 double* record);
+size_t uia_surface_ws_bytes(int B, int H, int W);
+int uia_surface_launch(hipStream_t stream, int B, int H, int W, const float* logits, const float* label, float percentile, void* ws, size_t ws_bytes,
+                       double* hd, double* asd);
 int uia_im2col_padded_launch(hipStream_t stream, int dtype, int B, int C, int H, int W, int P, const float* img, void* out, long ldo);
 int uia_embed_bwd_launch(hipStream_t stream, int rows, int D, int vocab, const int64_t* ids, const float* dx, float* dtable, long pad_id);
 int uia_embed_packed_launch(hipStream_t stream, int rows, int D, int vocab, int max_pos, const int64_t* ids, const int64_t* pos_idx, const float* table, const float* pos, const float* type0, float* out);

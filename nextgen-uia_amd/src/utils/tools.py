@@ -1,5 +1,5 @@
 """Logging / model summary / metric helpers used by the entry points (subset of /root/reference/src/utils/tools.py:37-206;
-HD95 / ASD (MONAI + scipy distance transforms on the host) and visualisation stay out of the hot path)."""
+HD95 / ASD run on the device (`uia_surface_distances`); visualisation stays out of the hot path)."""
 import ast
 import logging
 import os
@@ -80,9 +80,11 @@ class ScalarLog:
 
 class MetricAccumulator:
     """MetricAccumulator(type="seg") of the reference (tools.py:108-206) with the per-batch work on the device: update() enqueues the criterion, the
-    per-image Dice and IoU of the arg-max mask (losses/dice.py, MONAI semantics) and keeps the results as device tensors; compute() is the one host read and
-    returns the reference's keys — means / stds over the FINITE per-image values (np.std, population form, :148-163), `loss` the mean of the finite per-batch
-    losses.  hd95_* / asd_* are NaN: MONAI's surface distances are host-side scipy work outside this build."""
+    per-image Dice and IoU of the arg-max mask (losses/dice.py, MONAI semantics) and, for two-class device logits, the per-image HD95 and ASD (one
+    `uia_surface_distances` call: MONAI's compute_hausdorff_distance(percentile=95) / compute_average_surface_distance in pixels), and keeps the results as
+    device tensors; compute() is the one host read and returns the reference's keys — means / stds over the FINITE per-image values (np.std, population
+    form, :148-163; an empty prediction or ground truth makes an image's HD95 / ASD non-finite), `loss` the mean of the finite per-batch losses.
+    hd95_* / asd_* stay NaN for CPU tensors and for num_classes != 2 (per-class surface distances are not part of this build)."""
 
     def __init__(self, type="seg", criterion=None, num_classes=2):
         if type != "seg":
@@ -91,13 +93,17 @@ class MetricAccumulator:
         self.reset()
 
     def reset(self):
-        self._dice, self._iou, self._loss = [], [], []
+        self._dice, self._iou, self._loss, self._hd, self._asd = [], [], [], [], []
 
     def update(self, preds, labels):
-        from src.losses.dice import dice_per_image, iou_per_image
+        from src.losses.dice import dice_per_image, iou_per_image, surface_distances_per_image
         self._loss.append(self.criterion(preds.float(), labels.float()).detach().double().reshape(1))
         self._dice.append(dice_per_image(preds, labels))
         self._iou.append(iou_per_image(preds, labels))
+        if preds.is_cuda and preds.dim() == 4 and preds.shape[1] == 2 and self.num_classes == 2:
+            hd, asd = surface_distances_per_image(preds, labels, percentile=95)
+            self._hd.append(hd)
+            self._asd.append(asd)
 
     def compute(self):
         import numpy as np
@@ -106,12 +112,20 @@ class MetricAccumulator:
             nan = float("nan")
             return {k: nan for k in ("dice_mean", "dice_std", "iou_mean", "iou_std", "hd95_mean", "hd95_std", "asd_mean", "asd_std", "loss")}
         n = sum(t.numel() for t in self._dice)
-        flat = torch.cat(self._dice + self._iou + self._loss).cpu().numpy()       # one device-to-host copy
-        dice, iou, loss = flat[:n], flat[n:2 * n], flat[2 * n:]
+        nl = len(self._loss)
+        surf = len(self._hd) == len(self._dice)                                   # every batch went through the kernel
+        flat = torch.cat(self._dice + self._iou + self._loss + (self._hd + self._asd if surf else [])).cpu().numpy()       # one device-to-host copy
+        dice, iou, loss = flat[:n], flat[n:2 * n], flat[2 * n:2 * n + nl]
         fin = lambda a: a[np.isfinite(a)]
         nan = float("nan")
-        return {"dice_mean": float(np.mean(fin(dice))), "dice_std": float(np.std(fin(dice))), "iou_mean": float(np.mean(fin(iou))), "iou_std": float(np.std(fin(iou))),
-                "hd95_mean": nan, "hd95_std": nan, "asd_mean": nan, "asd_std": nan, "loss": float(np.mean(fin(loss)))}
+        # np.mean / np.std of no values: NaN, as the reference's compute() gives when every image is dropped
+        stat = lambda a, f: float(f(fin(a))) if np.isfinite(a).any() else nan
+        out = {"dice_mean": float(np.mean(fin(dice))), "dice_std": float(np.std(fin(dice))), "iou_mean": float(np.mean(fin(iou))), "iou_std": float(np.std(fin(iou))),
+               "hd95_mean": nan, "hd95_std": nan, "asd_mean": nan, "asd_std": nan, "loss": float(np.mean(fin(loss)))}
+        if surf:
+            hd, asd = flat[2 * n + nl:3 * n + nl], flat[3 * n + nl:]
+            out.update(hd95_mean=stat(hd, np.mean), hd95_std=stat(hd, np.std), asd_mean=stat(asd, np.mean), asd_std=stat(asd, np.std))
+        return out
 
 
 def report_test(args, stats, saved_best, rank=0):

@@ -1412,3 +1412,18 @@ def binary_cls_stats(p1, labels):
     rec = torch.empty(5, device=p1.device, dtype=torch.float64)
     check(lib().uia_binary_cls_stats(_stream(), N, _p(p1), _p(lab), _p(perm), _p(ws), ws.numel(), _p(rec)), "uia_binary_cls_stats")
     return rec
+
+
+def surface_distances(logits, label, percentile=95.0):
+    """logits [B,2,H,W] (non-fp32 is converted), label [B,1,H,W] -> (hd, asd) fp64 device tensors [B]: MONAI's percentile Hausdorff distance (symmetric) and
+    average surface distance (P -> G) of the arg-max mask against label > 0, in pixels; NaN where either mask is empty.  Enqueued only: nothing is read back."""
+    assert logits.dim() == 4 and logits.shape[1] == 2, f"surface_distances: logits must be [B, 2, H, W], got {tuple(logits.shape)}"
+    B, _, H, W = logits.shape
+    assert label.numel() == B * H * W and label.device == logits.device, f"surface_distances: label {tuple(label.shape)} does not match logits {tuple(logits.shape)}"
+    lg = logits.float().contiguous()
+    lab = label.reshape(B, 1, H, W).to(torch.float32).contiguous()
+    ws = torch.empty(lib().uia_surface_distances_workspace_bytes(B, H, W), device=lg.device, dtype=torch.uint8)
+    hd = torch.empty(B, device=lg.device, dtype=torch.float64)
+    asd = torch.empty(B, device=lg.device, dtype=torch.float64)
+    check(lib().uia_surface_distances(_stream(), B, H, W, _p(lg), _p(lab), float(percentile), _p(ws), ws.numel(), _p(hd), _p(asd)), "uia_surface_distances")
+    return hd, asd
