@@ -224,6 +224,12 @@ int uia_attn_bwd(void* stream, int dtype, const uia_attn_desc* d);
  * For A/B timing and tests. */
 int uia_attn_bwd_cfg(void* stream, int dtype, const uia_attn_desc* d, int cfg);
 
+/* softmax(q kᵀ·scale) v for sequences of any length L >= 1 (uia_attn_fwd stops at 272): online softmax over 64-key blocks, one
+ * workgroup per (batch, head, query block).  Head dim 64, no mask, no cu_seqlens, row-major out (out_kb_rows = 0); lse is written if
+ * non-null.  q / k / v / out 16-byte aligned, ld_qkv and ldo rows of whole 16-byte units.  Forward only (no long backward).
+ * Replaces the MemEffAttention of the DINOv2 tower (third_party/dino/vision_transformer.py [third-party], 1370 tokens at 518 px). */
+int uia_attn_fwd_long(void* stream, int dtype, const uia_attn_desc* d);
+
 /* ---------------------------------------------------------------------------------------------
  * LayerNorm over fp32 rows (model.py:163-169; timm / HF LayerNorm [third-party]).
  * x rows may be strided by ldx (elements); y / dy are compact [M,D].  Backward is for FROZEN
@@ -234,6 +240,13 @@ int uia_layernorm_fwd(void* stream, int dtype, int M, int D, int64_t ldx, const 
  * only if stats is given.  The deferred-residual form of uia_gemm (resid_ln_stats) consumes them. */
 int uia_layernorm_fwd_stats(void* stream, int dtype, int M, int D, int64_t ldx, const float* x, const float* gamma, const float* beta,
                             float eps, void* yT, float* y32, float* stats);
+/* out[b, :] = mean over rows l in [row0, row0+n) of LayerNorm(x[b, l, :]) (fp32; token rows ldx elements apart, images L·ldx apart;
+ * out rows ldo apart).  The patch-token pool of the DINOv2 classification head (dino/dinov2.py:33-100 [third-party]) without a
+ * normalised [B·L, D] tensor.  ws: B·UIA_POOL_SLICES·D floats of scratch.  Fixed summation order (bit-identical runs).
+ * D <= 1024, D % 4 == 0, every pointer 16-byte aligned. */
+#define UIA_POOL_SLICES 32
+int uia_ln_mean_rows(void* stream, int B, int L, int row0, int n, int D, int64_t ldx, const float* x, const float* gamma, const float* beta,
+                     float eps, float* ws, float* out, int64_t ldo);
 int uia_layernorm_bwd(void* stream, int dtype, int M, int D, int64_t ldx, const void* dy, const float* x, const float* gamma,
                       float eps, const float* dres, float* dx32, void* dxT);
 /* The same backward on THREE-BYTE tensors (bf16 launches, compact rows; the form is defined at uia_gemm_desc.resid_lo8): inside a frozen block

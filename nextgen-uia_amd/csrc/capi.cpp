@@ -50,6 +50,10 @@ int uia_attn_fwd(void* stream, int dtype, const uia_attn_desc* d) {
     NEED(d, "uia_attn_fwd");
     return uia_attn_fwd_launch((hipStream_t)stream, dtype, *d);
 }
+int uia_attn_fwd_long(void* stream, int dtype, const uia_attn_desc* d) {
+    NEED(d, "uia_attn_fwd_long");
+    return uia_attn_fwd_long_launch((hipStream_t)stream, dtype, *d);
+}
 int uia_attn_bwd(void* stream, int dtype, const uia_attn_desc* d) {
     NEED(d, "uia_attn_bwd");
     return uia_attn_bwd_launch((hipStream_t)stream, dtype, *d, 0);
@@ -223,3 +227,7 @@ int uia_embed_packed(void* stream, int rows, int D, int vocab, int max_pos, cons
 }
 
 }  // extern "C"
+int uia_ln_mean_rows(void* stream, int B, int L, int row0, int n, int D, int64_t ldx, const float* x, const float* gamma, const float* beta,
+                     float eps, float* ws, float* out, int64_t ldo) {
+    return uia_ln_mean_rows_launch((hipStream_t)stream, B, L, row0, n, D, (long)ldx, x, gamma, beta, eps, ws, out, (long)ldo);
+}

@@ -12,6 +12,7 @@ typedef uia_attn_desc UiaAttnParams;
 
 int uia_gemm_launch(hipStream_t stream, int dtype, const UiaGemmParams& p, int cfg);
 int uia_attn_fwd_launch(hipStream_t stream, int dtype, const UiaAttnParams& p);
+int uia_attn_fwd_long_launch(hipStream_t stream, int dtype, const UiaAttnParams& p);
 int uia_attn_bwd_launch(hipStream_t stream, int dtype, const UiaAttnParams& p, int cfg = 0);
 int uia_layernorm_fwd_launch(hipStream_t stream, int dtype, int M, int D, long ldx, const float* x, const float* gamma, const float* beta,
                              float eps, void* yT, float* y32, float* stats);
@@ -84,3 +85,5 @@ int uia_surface_launch(hipStream_t stream, int B, int H, int W, const float* log
 int uia_im2col_padded_launch(hipStream_t stream, int dtype, int B, int C, int H, int W, int P, const float* img, void* out, long ldo);
 int uia_embed_bwd_launch(hipStream_t stream, int rows, int D, int vocab, const int64_t* ids, const float* dx, float* dtable, long pad_id);
 int uia_embed_packed_launch(hipStream_t stream, int rows, int D, int vocab, int max_pos, const int64_t* ids, const int64_t* pos_idx, const float* table, const float* pos, const float* type0, float* out);
+int uia_ln_mean_rows_launch(hipStream_t stream, int B, int L, int row0, int n, int D, long ldx, const float* x, const float* gamma, const float* beta,
+                            float eps, float* ws, float* out, long ldo);

@@ -114,7 +114,10 @@ def prepare_model(args):
 
 
 def checkpoint_dict(model):
-    """reference :236-246: adapter heads as module state dicts plus the backbone's Mona parameters by full name."""
+    """reference :236-246: adapter heads as module state dicts plus the backbone's Mona parameters by full name.  A model with its own
+    `checkpoint_dict()` (the DINOv2 classifier: the head's state dict alone) saves that instead."""
+    if hasattr(model, "checkpoint_dict"):
+        return model.checkpoint_dict()
     return {"reduces": model.reduces.state_dict(), "blocks": model.blocks.state_dict(), "cls_head": model.cls_head.state_dict(),
             "mona": {n: p.data.clone() for n, p in model.named_parameters() if "mona" in n}}
 
@@ -220,13 +223,16 @@ def test(args, prepare=None):
     model = (prepare or prepare_model)(args)
     saved_best = os.path.join(args.train_snapshot_path, "best_model.pth")
     adapter_state_dict = torch.load(saved_best, map_location="cpu")
-    model.reduces.load_state_dict(adapter_state_dict["reduces"])
-    model.blocks.load_state_dict(adapter_state_dict["blocks"])
-    model.cls_head.load_state_dict(adapter_state_dict["cls_head"])
-    mona_state_dict = adapter_state_dict["mona"]
-    for name, param in model.named_parameters():                # :301-304 (copy_ instead of re-pointing .data: the T copies of the weights are keyed by version)
-        if "mona" in name:
-            param.copy_(mona_state_dict[name].to(param.device))
+    if hasattr(model, "load_checkpoint"):                       # the counterpart of a model's own checkpoint_dict()
+        model.load_checkpoint(adapter_state_dict)
+    else:
+        model.reduces.load_state_dict(adapter_state_dict["reduces"])
+        model.blocks.load_state_dict(adapter_state_dict["blocks"])
+        model.cls_head.load_state_dict(adapter_state_dict["cls_head"])
+        mona_state_dict = adapter_state_dict["mona"]
+        for name, param in model.named_parameters():            # :301-304 (copy_ instead of re-pointing .data: the T copies of the weights are keyed by version)
+            if "mona" in name:
+                param.copy_(mona_state_dict[name].to(param.device))
     UF.WEIGHTS.bump()
     model.eval()
     dm = dataset_cls.DataModule(args)

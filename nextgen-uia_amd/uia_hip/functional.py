@@ -21,6 +21,7 @@ import time
 import torch
 
 from . import ops
+from ._lib import UiaError
 
 _STATE = {"dtype": torch.bfloat16, "seed": 0x5EED, "calls": 0, "fwd_resid3": os.environ.get("UIA_FWD_RESID3", "1") != "0"}
 
@@ -859,6 +860,9 @@ class BlockSpec:
         self.ln1, self.qkv, self.proj, self.ln2, self.fc1, self.fc2 = ln1, qkv, proj, ln2, fc1, fc2   # each: (weight, bias)
 
 
+ATTN_SINGLE_PASS_MAX = 272       # longest sequence of uia_attn_fwd / uia_attn_bwd; longer ones take uia_attn_fwd_long (forward only)
+
+
 class VitBlockFn(torch.autograd.Function):
     """x + attn(LN1 x);  · + mlp(LN2 ·)   with frozen weights: the backward is dgrad only."""
 
@@ -866,6 +870,10 @@ class VitBlockFn(torch.autograd.Function):
     def forward(ctx, x, spec):
         B, N, D = x.shape
         M, dt = B * N, compute_dtype()
+        if N > ATTN_SINGLE_PASS_MAX and (ctx.needs_input_grad[0] or spec.mask is not None):
+            raise UiaError(f"vit_block: {N} tokens exceed the {ATTN_SINGLE_PASS_MAX} of the attention backward; sequences this long run forward-only "
+                           "(frozen tower under torch.no_grad()), unmasked" if ctx.needs_input_grad[0] else
+                           f"vit_block: {N} tokens with a mask: the long attention forward takes no mask")
         x3 = fwd3_of(x)                                   # the adapter in front handed its output over as a three-byte tensor (set_fwd_resid3): (hi = T rows, low bytes, row sums)
         like = x3[1] if x3 is not None else x
         if x3 is None:
@@ -888,9 +896,14 @@ class VitBlockFn(torch.autograd.Function):
             h1 = _empty((M, D), dt, x)
             ops.layernorm_fwd(x2d, spec.ln1[0], spec.ln1[1], spec.eps, y_t=h1)
             ops.gemm(h1, WEIGHTS.get(spec.qkv[0], dt), bias=spec.qkv[1], out_t=qkv)
-        a = _attn_act(M, D, dt, like, D) if D == 64 * spec.heads else _empty((M, D), dt, like)     # read by the output projection (and the backward kernel)
-        lse = torch.empty(B, spec.heads, N, device=like.device, dtype=torch.float32) if train else None
-        ops.attn_fwd(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], a, B, spec.heads, N, lse=lse, mask=spec.mask)
+        if N > ATTN_SINGLE_PASS_MAX:                         # long sequences (DINOv2 at 518 px: 1370 tokens): online-softmax forward, row-major output
+            a = _empty((M, D), dt, like)
+            ops.attn_fwd_long(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], a, B, spec.heads, N)
+            lse = None
+        else:
+            a = _attn_act(M, D, dt, like, D) if D == 64 * spec.heads else _empty((M, D), dt, like)     # read by the output projection (and the backward kernel)
+            lse = torch.empty(B, spec.heads, N, device=like.device, dtype=torch.float32) if train else None
+            ops.attn_fwd(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], a, B, spec.heads, N, lse=lse, mask=spec.mask)
         F = spec.fc1[0].shape[0]
         f = _act(M, F, dt, like, D)                          # fc1's result is read by fc2 only
         pre = _empty((M, F), dt, like) if train else None

@@ -842,6 +842,17 @@ def attn_fwd(q, k, v, out, B, H, L, lse=None, mask=None, keylen=None, scale=None
     check(lib().uia_attn_fwd(_stream(), _code(q.dtype), C.byref(d)), "uia_attn_fwd")
 
 
+def attn_fwd_long(q, k, v, out, B, H, L, lse=None, scale=None):
+    """uia_attn_fwd_long: softmax(q kᵀ·scale) v at any L (online softmax over 64-key blocks), head dim 64, no mask, row-major out.
+    Operand layout as attn_fwd: element (b, l, h, d) of q / k / v / out at row b*L + l, column h*64 + d (slices of the fused qkv are fine)."""
+    if is_kb(out):
+        raise UiaError("attn_fwd_long: the output must be a row-major tensor, not K-blocked")
+    d = _attn_desc(q, k, v, out, lse, B, H, L, None, None, scale)
+    if d.dh != 64:
+        raise UiaError(f"attn_fwd_long: head dim {d.dh}, only 64 is supported")
+    check(lib().uia_attn_fwd_long(_stream(), _code(q.dtype), C.byref(d)), "uia_attn_fwd_long")
+
+
 ATTN_BWD_CFG = 0     # uia_attn_bwd_cfg's kernel configuration (0 = the library's choice); tools and tests switch it for A/B runs
 
 
@@ -876,6 +887,24 @@ def layernorm_fwd(x, gamma, beta, eps, y_t=None, y32=None, rows=None, ldx=None, 
         check(lib().uia_layernorm_fwd_stats(_stream(), dt, rows, D, ldx, _p(x), _p(gamma), _p(beta), eps, _p(y_t), _p(y32), _p(stats)), "uia_layernorm_fwd_stats")
         return
     check(lib().uia_layernorm_fwd(_stream(), dt, rows, D, ldx, _p(x), _p(gamma), _p(beta), eps, _p(y_t), _p(y32)), "uia_layernorm_fwd")
+
+
+POOL_SLICES = 32      # UIA_POOL_SLICES of include/uia_hip.h
+
+
+def ln_mean_rows(x, gamma, beta, eps, row0, n, out=None):
+    """x fp32 [B, L, D]: out[b] = mean over rows row0 .. row0+n-1 of LayerNorm(x[b, l]) (uia_ln_mean_rows; fixed summation order)."""
+    if x.dim() != 3 or x.dtype != torch.float32 or x.stride(-1) != 1 or x.stride(1) != x.shape[2] or x.stride(0) != x.shape[1] * x.shape[2]:
+        raise UiaError("ln_mean_rows: x must be a contiguous fp32 [B, L, D] tensor")
+    B, L, D = x.shape
+    if out is None:
+        out = torch.empty(B, D, device=x.device, dtype=torch.float32)
+    if out.dtype != torch.float32 or out.stride(-1) != 1 or out.shape[-1] != D or out.shape[0] != B:
+        raise UiaError("ln_mean_rows: out must be fp32 [B, D] with unit column stride")
+    ws = torch.empty(B * POOL_SLICES * D, device=x.device, dtype=torch.float32)
+    check(lib().uia_ln_mean_rows(_stream(), B, L, int(row0), int(n), D, D, _p(x), _p(gamma), _p(beta), float(eps), _p(ws), _p(out), out.stride(0)),
+          "uia_ln_mean_rows")
+    return out
 
 
 def layernorm_bwd(dy, x, gamma, eps, dres=None, dx32=None, dx_t=None, rows=None, ldx=None, dx_lo=None):
