@@ -530,6 +530,51 @@ int uia_adamw_clip_step_guarded(void* stream, size_t n, float* p, float* acc, fl
                                 float eps, float weight_decay, float max_norm, float grad_scale, float skip_scale, float* ws8, int32_t* ctl);
 
 /* ---------------------------------------------------------------------------------------------
+ * DINOv2 UNet decoder (dino/dinov2.py:130-260 [third-party]): convolutions, BatchNorm + ReLU and resampling on NHWC activations
+ * (channels innermost).  Fixed reduction orders throughout: two identical calls give identical bits.
+ *
+ * uia_conv_igemm: implicit GEMM y[m][n] = Σ_k w[n][k]·x[m][k] (+ bias), x gathered per tap from the activation (no im2col).
+ *   UIA_CONV3      3x3, pad 1, stride 1 on a B×H×W grid.  Sources x1 [B,H,W,C1] and x2 [B,H,W,C2] (C2 = 0: none) are the channel
+ *                  halves of one input; w [N][9][C1+C2]; channels [0, N1) go to y1 [B,H,W,N1], [N1, N) to y2 [B,H,W,N−N1].  The data
+ *                  gradient is the same call on dy with the flipped, transposed weight.
+ *   UIA_CONVT_FWD  ConvTranspose2d k=2 s=2 of x1 [B,H,W,C1]: w [4·Cout][C1] (row (2·di+dj)·Cout + o), N = 4·Cout, N1 = N, bias [Cout];
+ *                  y1 [B,2H,2W,Cout].
+ *   UIA_CONVT_BWD  its data gradient: x1 = dy [B,2H,2W,C1 = Cout], w [N = Cin][4][Cout], y1 = dx [B,H,W,Cin], N1 = N.
+ *   bias: fp32 or null.  MFMA path when C1, C2 % 32 == 0, N, N1 (and Cout) % 4 == 0 and operands 16-byte aligned; a direct path otherwise.
+ * uia_conv_wgrad: fp32 weight gradient over the B×H×W pixels in uia_conv_wgrad_splits(...) pixel ranges added in range order.
+ *   UIA_CONV3      dw [N][9·(C1+C2)] from x1 / x2 and dy [B,H,W,N].
+ *   UIA_CONVT_FWD  dw [4·N][C1] from x1 [B,H,W,C1] and dy [B,2H,2W,N] (N = Cout).
+ *   ws: splits·rows·cols floats when splits > 1 (may be null otherwise). */
+enum { UIA_CONV3 = 0, UIA_CONVT_FWD = 1, UIA_CONVT_BWD = 2 };
+#define UIA_WGRAD_MAX_SPLITS 64            /* MFMA path (channels % 32, N % 8) */
+#define UIA_WGRAD_MAX_DIRECT_SPLITS 1024    /* direct path (few channels) */
+int uia_conv_igemm(void* stream, int dtype, int mode, int B, int H, int W, int C1, int C2, const void* x1, const void* x2, int N, int N1,
+                   const void* w, const float* bias, void* y1, void* y2);
+int uia_conv_wgrad_splits(int mode, int B, int H, int W, int C1, int C2, int N);
+int uia_conv_wgrad(void* stream, int dtype, int mode, int B, int H, int W, int C1, int C2, const void* x1, const void* x2, int N, const void* dy,
+                   float* ws, float* dw);
+/* BatchNorm2d (+ ReLU when relu != 0) on y [M = B·H·W, C] (dtype elements), fp32 parameters and buffers.
+ *   training: batch mean and biased variance; mean / invstd saved for the backward, running_mean / running_var updated with the unbiased
+ *   variance (momentum), *num_batches_tracked += 1 (either buffer pointer may be null: no update).  eval: the running statistics.
+ *   scale / shift [C] receive the folded affine, out = act(y·scale + shift).  ws: UIA_BN_SLICES·C·3 floats.
+ * uia_bn_relu_bwd: dy from dout through ReLU and the training-mode statistics; dgamma = Σdz·x̂, dbeta = Σdz (overwritten).
+ * uia_colsum_ordered: out[c] = Σ_m y[m][c] (fp32; the convs' bias gradients).  ws: UIA_BN_SLICES·C·3 floats. */
+#define UIA_BN_SLICES 256
+int uia_bn_fwd(void* stream, int dtype, int training, int64_t M, int C, const void* y, const float* gamma, const float* beta, float* running_mean,
+               float* running_var, int64_t* num_batches_tracked, float momentum, float eps, float* ws, float* mean, float* invstd, float* scale,
+               float* shift, int relu, void* out);
+int uia_bn_relu_bwd(void* stream, int dtype, int64_t M, int C, const void* y, const void* dout, const float* scale, const float* shift,
+                    const float* mean, const float* invstd, const float* gamma, float* ws, float* dgamma, float* dbeta, void* dy);
+int uia_colsum_ordered(void* stream, int dtype, int64_t M, int C, const void* y, float* ws, float* out);
+/* uia_upsample_ac: bilinear, align_corners=True, integer factor f on NHWC: forward in [B,H,W,C] -> out [B,fH,fW,C]; backward (gather,
+ *   no atomics) in = dout [B,fH,fW,C] -> out = dx [B,H,W,C].
+ * uia_resize_aa: F.interpolate(bicubic, antialias=True, align_corners=False) from NHWC x [B,Hi,Wi,C] (dtype) to NCHW fp32 out
+ *   [B,C,Ho,Wo] through tmp (fp32 [B,C,Hi,Wo]); backward: dout fp32 NCHW -> dx NHWC (dtype).  Downscale at most 3x. */
+int uia_upsample_ac(void* stream, int dtype, int backward, int B, int H, int W, int C, int f, const void* in, void* out);
+int uia_resize_aa(void* stream, int dtype, int backward, int B, int C, int Hi, int Wi, int Ho, int Wo, const void* x, float* tmp, float* out,
+                  const float* dout, void* dx);
+
+/* ---------------------------------------------------------------------------------------------
  * Data-parallel exchange (new: the reference is single-process, finetune.py:287-302 accumulates
  * instead).  RCCL all-reduce on the caller's stream; the unique id travels through the host.
  * Every RCCL failure is reported as "rank r/world: <call> failed: <reason>" through uia_last_error(). */

@@ -231,3 +231,34 @@ int uia_ln_mean_rows(void* stream, int B, int L, int row0, int n, int D, int64_t
                      float eps, float* ws, float* out, int64_t ldo) {
     return uia_ln_mean_rows_launch((hipStream_t)stream, B, L, row0, n, D, (long)ldx, x, gamma, beta, eps, ws, out, (long)ldo);
 }
+
+extern "C" {
+int uia_conv_igemm(void* stream, int dtype, int mode, int B, int H, int W, int C1, int C2, const void* x1, const void* x2, int N, int N1,
+                   const void* w, const float* bias, void* y1, void* y2) {
+    return uia_conv_igemm_launch((hipStream_t)stream, dtype, mode, B, H, W, C1, C2, x1, x2, N, N1, w, bias, y1, y2);
+}
+int uia_conv_wgrad(void* stream, int dtype, int mode, int B, int H, int W, int C1, int C2, const void* x1, const void* x2, int N, const void* dy,
+                   float* ws, float* dw) {
+    return uia_conv_wgrad_launch((hipStream_t)stream, dtype, mode, B, H, W, C1, C2, x1, x2, N, dy, ws, dw);
+}
+int uia_bn_fwd(void* stream, int dtype, int training, int64_t M, int C, const void* y, const float* gamma, const float* beta, float* running_mean,
+               float* running_var, int64_t* num_batches_tracked, float momentum, float eps, float* ws, float* mean, float* invstd, float* scale,
+               float* shift, int relu, void* out) {
+    return uia_bn_fwd_launch((hipStream_t)stream, dtype, training, (long)M, C, y, gamma, beta, running_mean, running_var, num_batches_tracked, momentum, eps,
+                             ws, mean, invstd, scale, shift, relu, out);
+}
+int uia_bn_relu_bwd(void* stream, int dtype, int64_t M, int C, const void* y, const void* dout, const float* scale, const float* shift,
+                    const float* mean, const float* invstd, const float* gamma, float* ws, float* dgamma, float* dbeta, void* dy) {
+    return uia_bn_relu_bwd_launch((hipStream_t)stream, dtype, (long)M, C, y, dout, scale, shift, mean, invstd, gamma, ws, dgamma, dbeta, dy);
+}
+int uia_colsum_ordered(void* stream, int dtype, int64_t M, int C, const void* y, float* ws, float* out) {
+    return uia_colsum_ordered_launch((hipStream_t)stream, dtype, (long)M, C, y, ws, out);
+}
+int uia_upsample_ac(void* stream, int dtype, int backward, int B, int H, int W, int C, int f, const void* in, void* out) {
+    return uia_upsample_ac_launch((hipStream_t)stream, dtype, backward, B, H, W, C, f, in, out);
+}
+int uia_resize_aa(void* stream, int dtype, int backward, int B, int C, int Hi, int Wi, int Ho, int Wo, const void* x, float* tmp, float* out,
+                  const float* dout, void* dx) {
+    return uia_resize_aa_launch((hipStream_t)stream, dtype, backward, B, C, Hi, Wi, Ho, Wo, x, tmp, out, dout, dx);
+}
+}  // extern "C"

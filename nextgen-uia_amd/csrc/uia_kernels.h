@@ -87,3 +87,17 @@ int uia_embed_bwd_launch(hipStream_t stream, int rows, int D, int vocab, const i
 int uia_embed_packed_launch(hipStream_t stream, int rows, int D, int vocab, int max_pos, const int64_t* ids, const int64_t* pos_idx, const float* table, const float* pos, const float* type0, float* out);
 int uia_ln_mean_rows_launch(hipStream_t stream, int B, int L, int row0, int n, int D, long ldx, const float* x, const float* gamma, const float* beta,
                             float eps, float* ws, float* out, long ldo);
+int uia_conv_igemm_launch(hipStream_t stream, int dtype, int mode, int B, int H, int W, int C1, int C2, const void* x1, const void* x2, int N, int N1,
+                          const void* w, const float* bias, void* y1, void* y2);
+int uia_conv_wgrad_splits(int mode, int B, int H, int W, int C1, int C2, int N);
+int uia_conv_wgrad_launch(hipStream_t stream, int dtype, int mode, int B, int H, int W, int C1, int C2, const void* x1, const void* x2, int N,
+                          const void* dy, float* ws, float* dw);
+int uia_bn_fwd_launch(hipStream_t stream, int dtype, int training, long M, int C, const void* y, const float* gamma, const float* beta,
+                      float* run_mean, float* run_var, int64_t* nbt, float momentum, float eps, float* ws, float* mean, float* invstd,
+                      float* scale, float* shift, int relu, void* out);
+int uia_bn_relu_bwd_launch(hipStream_t stream, int dtype, long M, int C, const void* y, const void* dout, const float* scale, const float* shift,
+                           const float* mean, const float* invstd, const float* gamma, float* ws, float* dgamma, float* dbeta, void* dy);
+int uia_colsum_ordered_launch(hipStream_t stream, int dtype, long M, int C, const void* y, float* ws, float* out);
+int uia_upsample_ac_launch(hipStream_t stream, int dtype, int backward, int B, int H, int W, int C, int f, const void* in, void* out);
+int uia_resize_aa_launch(hipStream_t stream, int dtype, int backward, int B, int C, int Hi, int Wi, int Ho, int Wo, const void* x, float* tmp, float* out,
+                         const float* dout, void* dx);

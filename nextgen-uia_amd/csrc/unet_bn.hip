@@ -1,0 +1,228 @@
+// unet_bn.hip — BatchNorm2d + ReLU of the DINOv2 UNet decoder on NHWC rows [M = B·H·W, C], and plain column sums (the convs' bias
+// gradients).
+//
+// Replaces: nn.BatchNorm2d(eps 1e-5, momentum 0.1) + nn.ReLU of UNetDecoderUpBlock (the reference's src/third_party/dino/dinov2.py:130-152)
+//           in training and eval mode, forward and backward.
+//
+// Every reduction runs in two launches with a fixed order (no atomics, bit-identical from run to run):
+//   1. grid S (at most UIA_BN_SLICES): workgroup s takes a contiguous run of rows; its threads own (channel, row lane) pairs, each sums
+//      its rows in order and the row lanes are added in lane order through LDS: two floats per (slice, channel).
+//   2. one thread per channel adds the slices in slice order.
+// The batch statistics are summed shifted by the slice's first row (Σ(y − K), Σ(y − K)²) and combined with Chan's formula, so a large
+// mean does not cancel the variance.  Nothing is read back on the host: the running buffers and num_batches_tracked are updated here.
+#include "uia_common.h"
+#include "uia_kernels.h"
+
+namespace {
+
+enum { RED_STATS = 0, RED_BWD = 1, RED_SUM = 2 };
+
+// ws[(s·C + c)·3 + {0,1,2}]: RED_STATS {Σ(y−K), Σ(y−K)², K}; RED_BWD {Σdz, Σdz·x̂, 0}; RED_SUM {Σy, 0, 0}
+template <typename T, int MODE>
+__global__ __launch_bounds__(256) void reduce_kernel(long M, int C, const T* __restrict__ y, const T* __restrict__ dout,
+                                                     const float* __restrict__ scale, const float* __restrict__ shift,
+                                                     const float* __restrict__ mean, const float* __restrict__ invstd, float* __restrict__ ws) {
+    __shared__ float red[2][256];
+    const int S = gridDim.x, s = blockIdx.x, tid = threadIdx.x;
+    const long per = (M + S - 1) / S;
+    const long rb = (long)s * per, re = rb + per < M ? rb + per : M;
+    const int Cb = C < 256 ? C : 256, RP = 256 / Cb;
+    for (int cbase = 0; cbase < C; cbase += Cb) {
+        const int c = cbase + tid % Cb, rl = tid / Cb;
+        const bool act = rl < RP && c < C;
+        float a = 0.f, q = 0.f, K = 0.f;
+        if (act && rb < re) {
+            if (MODE == RED_STATS) K = to_f32(y[rb * C + c]);
+            float sc = 0.f, sh = 0.f, mu = 0.f, is = 0.f;
+            if (MODE == RED_BWD) { sc = scale[c]; sh = shift[c]; mu = mean[c]; is = invstd[c]; }
+            for (long r = rb + rl; r < re; r += RP) {
+                const float v = to_f32(y[r * C + c]);
+                if (MODE == RED_STATS) {
+                    const float d = v - K;
+                    a += d;
+                    q = fmaf(d, d, q);
+                } else if (MODE == RED_BWD) {
+                    const float dz = fmaf(v, sc, sh) > 0.f ? to_f32(dout[r * C + c]) : 0.f;
+                    a += dz;
+                    q = fmaf(dz, (v - mu) * is, q);
+                } else {
+                    a += v;
+                }
+            }
+        }
+        red[0][tid] = a;
+        red[1][tid] = q;
+        __syncthreads();
+        if (rl == 0 && c < C) {
+            for (int k = 1; k < RP; ++k) {
+                a += red[0][tid + k * Cb];
+                q += red[1][tid + k * Cb];
+            }
+            float* o = ws + ((size_t)s * C + c) * 3;
+            o[0] = a;
+            o[1] = q;
+            o[2] = K;
+        }
+        __syncthreads();
+    }
+}
+
+// train-mode statistics: mean, 1/std, the affine scale / shift of the apply, running buffers
+__global__ __launch_bounds__(256) void bn_finalize_kernel(long M, int C, int S, const float* __restrict__ ws, const float* __restrict__ gamma,
+                                                          const float* __restrict__ beta, float eps, float momentum, float* __restrict__ mean,
+                                                          float* __restrict__ invstd, float* __restrict__ scale, float* __restrict__ shift,
+                                                          float* __restrict__ run_mean, float* __restrict__ run_var, int64_t* __restrict__ nbt) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c == 0 && nbt) nbt[0] += 1;
+    if (c >= C) return;
+    const long per = (M + S - 1) / S;
+    double n = 0.0, mu = 0.0, m2 = 0.0;      // Chan's parallel combination, slice by slice (fp64 only for these few per-channel scalars)
+    for (int s = 0; s < S; ++s) {
+        const long rb = (long)s * per, re = rb + per < M ? rb + per : M;
+        if (re <= rb) continue;
+        const double ns = (double)(re - rb);
+        const float* o = ws + ((size_t)s * C + c) * 3;
+        const double ms = (double)o[2] + (double)o[0] / ns;
+        const double m2s = (double)o[1] - (double)o[0] * (double)o[0] / ns;
+        const double nn = n + ns, d = ms - mu;
+        mu += d * ns / nn;
+        m2 += m2s + d * d * n * ns / nn;
+        n = nn;
+    }
+    const double var = m2 > 0.0 ? m2 / n : 0.0;
+    const float is = (float)(1.0 / sqrt(var + (double)eps));
+    mean[c] = (float)mu;
+    invstd[c] = is;
+    const float g = gamma[c] * is;
+    scale[c] = g;
+    shift[c] = beta[c] - (float)mu * g;
+    if (run_mean) {
+        run_mean[c] = (1.f - momentum) * run_mean[c] + momentum * (float)mu;
+        run_var[c] = (1.f - momentum) * run_var[c] + momentum * (float)(n > 1.0 ? m2 / (n - 1.0) : var);
+    }
+}
+
+__global__ __launch_bounds__(256) void bn_eval_coeff_kernel(int C, const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                            const float* __restrict__ run_mean, const float* __restrict__ run_var, float eps,
+                                                            float* __restrict__ scale, float* __restrict__ shift) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= C) return;
+    const float g = gamma[c] / sqrtf(run_var[c] + eps);
+    scale[c] = g;
+    shift[c] = beta[c] - run_mean[c] * g;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void bn_apply_kernel(long n, int C, const T* __restrict__ y, const float* __restrict__ scale,
+                                                       const float* __restrict__ shift, int relu, T* __restrict__ out) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int c = (int)(i % C);
+    float v = fmaf(to_f32(y[i]), scale[c], shift[c]);
+    if (relu) v = v > 0.f ? v : 0.f;
+    out[i] = from_f32<T>(v);
+}
+
+// column sums (RED_SUM) or the two BN backward sums (RED_BWD), slices added in order
+__global__ __launch_bounds__(256) void col_finalize_kernel(int C, int S, const float* __restrict__ ws, float* __restrict__ o0, float* __restrict__ o1) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= C) return;
+    float a = 0.f, q = 0.f;
+    for (int s = 0; s < S; ++s) {
+        a += ws[((size_t)s * C + c) * 3];
+        q += ws[((size_t)s * C + c) * 3 + 1];
+    }
+    o0[c] = a;
+    if (o1) o1[c] = q;
+}
+
+// dy = γ·r·(dz − Σdz/M − x̂·Σ(dz·x̂)/M), dz = dout·[y·scale + shift > 0]
+template <typename T>
+__global__ __launch_bounds__(256) void bn_bwd_apply_kernel(long M, int C, const T* __restrict__ y, const T* __restrict__ dout, const float* __restrict__ scale,
+                                                           const float* __restrict__ shift, const float* __restrict__ mean, const float* __restrict__ invstd,
+                                                           const float* __restrict__ gamma, const float* __restrict__ dbeta, const float* __restrict__ dgamma,
+                                                           T* __restrict__ dy) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= M * C) return;
+    const int c = (int)(i % C);
+    const float v = to_f32(y[i]);
+    const float dz = fmaf(v, scale[c], shift[c]) > 0.f ? to_f32(dout[i]) : 0.f;
+    const float is = invstd[c], xh = (v - mean[c]) * is, inv = 1.0f / (float)M;
+    dy[i] = from_f32<T>(gamma[c] * is * (dz - dbeta[c] * inv - xh * dgamma[c] * inv));
+}
+
+int slices_for(long M) { long s = (M + 255) / 256; return (int)(s < UIA_BN_SLICES ? s : UIA_BN_SLICES); }
+
+}  // namespace
+
+#define BN_ARGS_OK(fn)                                                                                                      \
+    UIA_CHECK_ARG(dtype == UIA_F32 || dtype == UIA_BF16, fn ": dtype must be UIA_F32 or UIA_BF16");                       \
+    UIA_CHECK_ARG(M > 0 && C > 0 && C <= 65536 && M < (1l << 40), fn ": M=%ld C=%d out of range", (long)M, C)
+
+int uia_colsum_ordered_launch(hipStream_t stream, int dtype, long M, int C, const void* y, float* ws, float* out) {
+    BN_ARGS_OK("uia_colsum_ordered");
+    UIA_CHECK_ARG(y && ws && out, "uia_colsum_ordered: null tensor");
+    const int S = slices_for(M);
+    if (dtype == UIA_BF16)
+        hipLaunchKernelGGL((reduce_kernel<bf16_t, RED_SUM>), dim3(S), dim3(256), 0, stream, M, C, (const bf16_t*)y, nullptr, nullptr, nullptr, nullptr, nullptr, ws);
+    else
+        hipLaunchKernelGGL((reduce_kernel<float, RED_SUM>), dim3(S), dim3(256), 0, stream, M, C, (const float*)y, nullptr, nullptr, nullptr, nullptr, nullptr, ws);
+    UIA_CHECK_LAUNCH();
+    hipLaunchKernelGGL(col_finalize_kernel, dim3((C + 255) / 256), dim3(256), 0, stream, C, S, ws, out, nullptr);
+    UIA_CHECK_LAUNCH();
+    return 0;
+}
+
+int uia_bn_fwd_launch(hipStream_t stream, int dtype, int training, long M, int C, const void* y, const float* gamma, const float* beta,
+                      float* run_mean, float* run_var, int64_t* nbt, float momentum, float eps, float* ws, float* mean, float* invstd,
+                      float* scale, float* shift, int relu, void* out) {
+    BN_ARGS_OK("uia_bn_fwd");
+    UIA_CHECK_ARG(y && gamma && beta && scale && shift && out, "uia_bn_fwd: null tensor");
+    UIA_CHECK_ARG(eps > 0.f && momentum >= 0.f && momentum <= 1.f, "uia_bn_fwd: eps must be > 0 and momentum in [0, 1]");
+    if (training) {
+        UIA_CHECK_ARG(ws && mean && invstd, "uia_bn_fwd: training needs ws, mean and invstd");
+        UIA_CHECK_ARG((run_mean == nullptr) == (run_var == nullptr), "uia_bn_fwd: running mean and variance come together");
+        const int S = slices_for(M);
+        if (dtype == UIA_BF16)
+            hipLaunchKernelGGL((reduce_kernel<bf16_t, RED_STATS>), dim3(S), dim3(256), 0, stream, M, C, (const bf16_t*)y, nullptr, nullptr, nullptr, nullptr, nullptr, ws);
+        else
+            hipLaunchKernelGGL((reduce_kernel<float, RED_STATS>), dim3(S), dim3(256), 0, stream, M, C, (const float*)y, nullptr, nullptr, nullptr, nullptr, nullptr, ws);
+        UIA_CHECK_LAUNCH();
+        hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + 255) / 256), dim3(256), 0, stream, M, C, S, ws, gamma, beta, eps, momentum, mean, invstd, scale, shift,
+                           run_mean, run_var, nbt);
+    } else {
+        UIA_CHECK_ARG(run_mean && run_var, "uia_bn_fwd: eval mode needs the running buffers");
+        hipLaunchKernelGGL(bn_eval_coeff_kernel, dim3((C + 255) / 256), dim3(256), 0, stream, C, gamma, beta, run_mean, run_var, eps, scale, shift);
+    }
+    UIA_CHECK_LAUNCH();
+    const long n = M * C;
+    if (dtype == UIA_BF16)
+        hipLaunchKernelGGL(bn_apply_kernel<bf16_t>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, n, C, (const bf16_t*)y, scale, shift, relu, (bf16_t*)out);
+    else
+        hipLaunchKernelGGL(bn_apply_kernel<float>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, n, C, (const float*)y, scale, shift, relu, (float*)out);
+    UIA_CHECK_LAUNCH();
+    return 0;
+}
+
+int uia_bn_relu_bwd_launch(hipStream_t stream, int dtype, long M, int C, const void* y, const void* dout, const float* scale, const float* shift,
+                           const float* mean, const float* invstd, const float* gamma, float* ws, float* dgamma, float* dbeta, void* dy) {
+    BN_ARGS_OK("uia_bn_relu_bwd");
+    UIA_CHECK_ARG(y && dout && scale && shift && mean && invstd && gamma && ws && dgamma && dbeta && dy, "uia_bn_relu_bwd: null tensor");
+    const int S = slices_for(M);
+    if (dtype == UIA_BF16)
+        hipLaunchKernelGGL((reduce_kernel<bf16_t, RED_BWD>), dim3(S), dim3(256), 0, stream, M, C, (const bf16_t*)y, (const bf16_t*)dout, scale, shift, mean, invstd, ws);
+    else
+        hipLaunchKernelGGL((reduce_kernel<float, RED_BWD>), dim3(S), dim3(256), 0, stream, M, C, (const float*)y, (const float*)dout, scale, shift, mean, invstd, ws);
+    UIA_CHECK_LAUNCH();
+    hipLaunchKernelGGL(col_finalize_kernel, dim3((C + 255) / 256), dim3(256), 0, stream, C, S, ws, dbeta, dgamma);
+    UIA_CHECK_LAUNCH();
+    const long n = M * C;
+    if (dtype == UIA_BF16)
+        hipLaunchKernelGGL(bn_bwd_apply_kernel<bf16_t>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, M, C, (const bf16_t*)y, (const bf16_t*)dout, scale, shift,
+                           mean, invstd, gamma, dbeta, dgamma, (bf16_t*)dy);
+    else
+        hipLaunchKernelGGL(bn_bwd_apply_kernel<float>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, M, C, (const float*)y, (const float*)dout, scale, shift,
+                           mean, invstd, gamma, dbeta, dgamma, (float*)dy);
+    UIA_CHECK_LAUNCH();
+    return 0;
+}

@@ -106,7 +106,10 @@ def prepare_model(args):
 
 
 def checkpoint_dict(model):
-    """reference :212-225: adapter heads as module state dicts plus the backbone's Mona parameters by full name."""
+    """reference :212-225: adapter heads as module state dicts plus the backbone's Mona parameters by full name.  A model with its own
+    `checkpoint_dict()` (DINOv2 segmentation) decides its checkpoint contents."""
+    if hasattr(model, "checkpoint_dict"):
+        return model.checkpoint_dict()
     return {"reduces": model.reduces.state_dict(), "blocks": model.blocks.state_dict(), "seg_head": model.seg_head.state_dict(),
             "mona": {n: p.data.clone() for n, p in model.named_parameters() if "mona" in n}}
 
@@ -120,7 +123,8 @@ def evaluate(model, loader_pf, args, accumulator):
             accumulator.update(model(images).detach(), labels.detach())
 
 
-def train(args):
+def train(args, prepare=None):
+    """prepare: args -> model (default: this entry point's prepare_model; the DINOv2 segmentation entry point passes its own)."""
     rank, _, world = dist_env()
     if not torch.cuda.is_initialized():
         torch.set_num_threads(max(1, min(4, torch.get_num_threads())))
@@ -130,7 +134,7 @@ def train(args):
     bind_device(args)                                          # data parallel: cuda:LOCAL_RANK before anything is allocated
     UF.set_compute_dtype(torch.bfloat16 if args.dtype == "bf16" else torch.float32)
     UF.set_dropout_seed(args.seed + 7919 * rank)
-    model = prepare_model(args)
+    model = (prepare or prepare_model)(args)
     model.train()
     logging.info(model_summary({"model": model}))
     writer = ScalarLog(args.train_snapshot_path + "/log")
@@ -218,8 +222,8 @@ def train(args):
 
 
 @torch.no_grad()
-def test(args):
-    """reference :283-355."""
+def test(args, prepare=None):
+    """reference :283-355.  A model with `load_checkpoint(state)` loads best_model.pth itself."""
     logging.info("Start testing")
     rank, _, _ = dist_env()
     dm = dataset_seg.DataModule(args, rank=0, world=1)          # every rank evaluates the whole split
@@ -227,17 +231,13 @@ def test(args):
     dm.start_workers()
     bind_device(args)
     UF.set_compute_dtype(torch.bfloat16 if args.dtype == "bf16" else torch.float32)
-    model = prepare_model(args)
+    model = (prepare or prepare_model)(args)
     saved_best = os.path.join(args.train_snapshot_path, "best_model.pth")
     adapter_state_dict = torch.load(saved_best, map_location="cpu")
-    model.reduces.load_state_dict(adapter_state_dict["reduces"])
-    model.blocks.load_state_dict(adapter_state_dict["blocks"])
-    model.seg_head.load_state_dict(adapter_state_dict["seg_head"])
-    mona_state_dict = adapter_state_dict["mona"]
-    with torch.no_grad():
-        for name, param in model.named_parameters():            # :297-300 (copy_ instead of re-pointing .data: the T copies of the weights are keyed by version)
-            if "mona" in name:
-                param.copy_(mona_state_dict[name].to(param.device))
+    if hasattr(model, "load_checkpoint"):
+        model.load_checkpoint(adapter_state_dict)
+    else:
+        _load_adapter_checkpoint(model, adapter_state_dict)
     model.eval()
     if rank == 0:
         fresh_viz_dir(args)
@@ -250,6 +250,17 @@ def test(args):
     dm.shutdown()
     stats["results_csv"] = report_test(args, stats, saved_best, rank)
     return stats
+
+
+def _load_adapter_checkpoint(model, adapter_state_dict):
+    model.reduces.load_state_dict(adapter_state_dict["reduces"])
+    model.blocks.load_state_dict(adapter_state_dict["blocks"])
+    model.seg_head.load_state_dict(adapter_state_dict["seg_head"])
+    mona_state_dict = adapter_state_dict["mona"]
+    with torch.no_grad():
+        for name, param in model.named_parameters():            # :297-300 (copy_ instead of re-pointing .data: the T copies of the weights are keyed by version)
+            if "mona" in name:
+                param.copy_(mona_state_dict[name].to(param.device))
 
 
 def main(argv=None):

@@ -101,6 +101,14 @@ PROTOTYPES = {
     "uia_layernorm_fwd": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, i64, vp, vp, vp, f32, vp, vp]),
     "uia_layernorm_fwd_stats": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, i64, vp, vp, vp, f32, vp, vp, vp]),
     "uia_ln_mean_rows": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, i64, vp, vp, vp, f32, vp, vp, i64]),
+    "uia_conv_igemm": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp]),
+    "uia_conv_wgrad_splits": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "uia_conv_wgrad": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, vp]),
+    "uia_bn_fwd": (C.c_int, [vp, C.c_int, C.c_int, i64, C.c_int, vp, vp, vp, vp, vp, vp, f32, f32, vp, vp, vp, vp, vp, C.c_int, vp]),
+    "uia_bn_relu_bwd": (C.c_int, [vp, C.c_int, i64, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "uia_colsum_ordered": (C.c_int, [vp, C.c_int, i64, C.c_int, vp, vp, vp]),
+    "uia_upsample_ac": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
+    "uia_resize_aa": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp]),
     "uia_layernorm_bwd": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, i64, vp, vp, vp, f32, vp, vp, vp]),
     "uia_ln_lora_down": (C.c_int, [vp, C.c_int, C.POINTER(LnLoraDesc)]),
     "uia_lora_rank_update": (C.c_int, [vp, C.c_int, C.POINTER(LoraRankDesc)]),

@@ -2095,3 +2095,96 @@ def trainable_cls_head(tokens, ln_w, ln_b, eps, proj_w):
     cls = tokens[:, 0, :].contiguous()
     h = LayerNormAffineFn.apply(cls, ln_w, ln_b, eps)
     return LinearTrainFn.apply(CastFn.apply(h), proj_w, None, None, None, True)
+
+
+# ---------------------------------------------------------------- DINOv2 UNet decoder (NHWC activations in the compute dtype)
+def conv3_rows(w, dt):
+    """Conv2d weight [Cout, Cin, 3, 3] -> the implicit GEMM's rows [Cout, 9·Cin] (k = (3·ky + kx)·Cin + c)."""
+    return w.detach().permute(0, 2, 3, 1).reshape(w.shape[0], -1).to(dt).contiguous()
+
+
+def conv3_dgrad_rows(w, dt):
+    """The data gradient's weight: flipped taps, transposed channels -> [Cin, 9·Cout]."""
+    return w.detach().flip(2, 3).permute(1, 2, 3, 0).reshape(w.shape[1], -1).to(dt).contiguous()
+
+
+class UnetConvBNReLUFn(torch.autograd.Function):
+    """ReLU(BatchNorm2d(Conv2d3x3(cat[x1, x2]) + b)) on NHWC x1 [B,H,W,C1], x2 [B,H,W,C2] (x2 may be None); the concatenation is never
+    written.  training: batch statistics, running buffers updated on the device; eval: the running statistics (no backward)."""
+
+    @staticmethod
+    def forward(ctx, x1, x2, w, b, gamma, beta, running_mean, running_var, nbt, training, momentum, eps):
+        dt = x1.dtype
+        y = ops.conv_igemm(ops.CONV3, x1, x2, conv3_rows(w, dt), w.shape[0], bias=b.detach().contiguous())
+        out, mean, invstd, scale, shift = ops.bn_fwd(y, gamma.detach(), beta.detach(), running_mean, running_var, nbt, training, momentum, eps)
+        if training:
+            ctx.save_for_backward(x1, x2, w, y, gamma, mean, invstd, scale, shift)
+        ctx.training = training
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        if not ctx.training:
+            raise UiaError("UnetConvBNReLUFn: eval-mode BatchNorm has no backward here (the decoder trains in train mode)")
+        x1, x2, w, y, gamma, mean, invstd, scale, shift = ctx.saved_tensors
+        dy, dgamma, dbeta = ops.bn_relu_bwd(y, dout.contiguous(), scale, shift, mean, invstd, gamma.detach())
+        N, Cin = w.shape[0], w.shape[1]
+        dw = ops.conv_wgrad(ops.CONV3, x1, x2, dy, N).reshape(N, 3, 3, Cin).permute(0, 3, 1, 2).contiguous()
+        db = ops.colsum_ordered(dy)
+        dx1 = dx2 = None
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            C1 = x1.shape[3]
+            r = ops.conv_igemm(ops.CONV3, dy, None, conv3_dgrad_rows(w, dy.dtype), Cin, n1=C1)
+            dx1, dx2 = (r if x2 is not None else (r, None))
+        return dx1, dx2, dw, db, dgamma, dbeta, None, None, None, None, None, None
+
+
+class UnetConvTransposeFn(torch.autograd.Function):
+    """ConvTranspose2d(k=2, s=2) on NHWC x [B,h,w,Cin] -> [B,2h,2w,Cout]; weight [Cin, Cout, 2, 2] as nn.ConvTranspose2d keeps it."""
+
+    @staticmethod
+    def forward(ctx, x, w, b):
+        dt = x.dtype
+        Cin, Cout = w.shape[0], w.shape[1]
+        rows = w.detach().permute(2, 3, 1, 0).reshape(4 * Cout, Cin).to(dt).contiguous()
+        ctx.save_for_backward(x, w)
+        return ops.conv_igemm(ops.CONVT_FWD, x, None, rows, 4 * Cout, bias=b.detach().contiguous())
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w = ctx.saved_tensors
+        dy = dy.contiguous()
+        Cin, Cout = w.shape[0], w.shape[1]
+        dw = ops.conv_wgrad(ops.CONVT_FWD, x, None, dy, Cout).reshape(2, 2, Cout, Cin).permute(3, 2, 0, 1).contiguous()
+        db = ops.colsum_ordered(dy)
+        dx = None
+        if ctx.needs_input_grad[0]:
+            wb = w.detach().permute(0, 2, 3, 1).reshape(Cin, 4 * Cout).to(dy.dtype).contiguous()
+            dx = ops.conv_igemm(ops.CONVT_BWD, dy, None, wb, Cin)
+        return dx, dw, db
+
+
+class UpsampleACFn(torch.autograd.Function):
+    """nn.Upsample(scale_factor=f, bilinear, align_corners=True) on NHWC, integer f; the backward in gather form."""
+
+    @staticmethod
+    def forward(ctx, x, f):
+        ctx.f = int(f)
+        return ops.upsample_ac(x, f)
+
+    @staticmethod
+    def backward(ctx, dy):
+        return ops.upsample_ac(dy.contiguous(), ctx.f, backward=True), None
+
+
+class ResizeAAFn(torch.autograd.Function):
+    """F.interpolate(size, bicubic, antialias=True, align_corners=False) of NHWC x -> NCHW fp32 (the decoder's logits)."""
+
+    @staticmethod
+    def forward(ctx, x, size):
+        ctx.hw, ctx.dt = (x.shape[1], x.shape[2]), x.dtype
+        return ops.resize_aa(x, size)
+
+    @staticmethod
+    def backward(ctx, dy):
+        return ops.resize_aa_bwd(dy.contiguous().float(), ctx.hw, ctx.dt), None

@@ -1456,3 +1456,161 @@ def surface_distances(logits, label, percentile=95.0):
     asd = torch.empty(B, device=lg.device, dtype=torch.float64)
     check(lib().uia_surface_distances(_stream(), B, H, W, _p(lg), _p(lab), float(percentile), _p(ws), ws.numel(), _p(hd), _p(asd)), "uia_surface_distances")
     return hd, asd
+
+
+# ---------------------------------------------------------------- DINOv2 UNet decoder (csrc/unet_conv.hip, unet_bn.hip, unet_resample.hip)
+CONV3, CONVT_FWD, CONVT_BWD = 0, 1, 2      # uia_conv_igemm / uia_conv_wgrad modes
+BN_SLICES = 256                            # UIA_BN_SLICES
+
+
+def _nhwc(t, name, dt=None):
+    if t is None or t.dim() != 4 or not t.is_contiguous():
+        raise UiaError(f"{name}: a contiguous NHWC [B, H, W, C] tensor is required")
+    if dt is not None and t.dtype != dt:
+        raise UiaError(f"{name}: dtype {t.dtype}, expected {dt}")
+    return t
+
+
+def conv_igemm(mode, x1, x2, w, n, bias=None, n1=None):
+    """uia_conv_igemm.  CONV3: x1 [B,H,W,C1] (+ x2 [B,H,W,C2]) NHWC, w [n, 9·(C1+C2)] -> y [B,H,W,n], or (y1, y2) split at channel n1.
+    CONVT_FWD: x1 [B,h,w,Cin], w [4·Cout, Cin], n = 4·Cout -> [B,2h,2w,Cout].  CONVT_BWD: x1 = dy [B,2h,2w,Cout], w [Cin, 4·Cout], n = Cin -> [B,h,w,Cin]."""
+    _nhwc(x1, "conv_igemm x1")
+    dt = x1.dtype
+    B, H, W, C1 = x1.shape
+    C2 = 0
+    if x2 is not None:
+        _nhwc(x2, "conv_igemm x2", dt)
+        if tuple(x2.shape[:3]) != (B, H, W):
+            raise UiaError("conv_igemm: the two sources must share the pixel grid")
+        C2 = x2.shape[3]
+    if mode == CONVT_BWD:
+        H, W = H // 2, W // 2
+        if tuple(x1.shape[1:3]) != (2 * H, 2 * W):
+            raise UiaError("conv_igemm: the transposed conv's gradient grid must be even")
+    taps = {CONV3: 9, CONVT_FWD: 1, CONVT_BWD: 4}[mode]
+    if w.dtype != dt or not w.is_contiguous() or tuple(w.shape) != (n, taps * (C1 + C2)):
+        raise UiaError(f"conv_igemm: w must be contiguous {dt} [{n}, {taps * (C1 + C2)}], got {w.dtype} {tuple(w.shape)}")
+    if bias is not None:
+        nb = n // 4 if mode == CONVT_FWD else n
+        if bias.dtype != torch.float32 or not bias.is_contiguous() or bias.numel() != nb:
+            raise UiaError(f"conv_igemm: bias must be contiguous fp32 [{nb}]")
+    n1 = n if n1 is None else int(n1)
+    if mode == CONVT_FWD:
+        y1 = torch.empty(B, 2 * H, 2 * W, n // 4, device=x1.device, dtype=dt)
+    else:
+        y1 = torch.empty(B, H, W, n1, device=x1.device, dtype=dt)
+    y2 = torch.empty(B, H, W, n - n1, device=x1.device, dtype=dt) if n1 < n else None
+    check(lib().uia_conv_igemm(_stream(), _code(dt), mode, B, H, W, C1, C2, _p(x1), _p(x2), n, n1, _p(w), _p(bias), _p(y1), _p(y2)), "uia_conv_igemm")
+    return y1 if y2 is None else (y1, y2)
+
+
+def conv_wgrad(mode, x1, x2, dy, n):
+    """uia_conv_wgrad -> fp32 dW.  CONV3: dy [B,H,W,n] -> [n, 9·(C1+C2)].  CONVT_FWD: x1 [B,h,w,Cin], dy [B,2h,2w,n = Cout] -> [4·n, Cin]."""
+    _nhwc(x1, "conv_wgrad x1")
+    _nhwc(dy, "conv_wgrad dy", x1.dtype)
+    B, H, W, C1 = x1.shape
+    C2 = 0
+    if x2 is not None:
+        _nhwc(x2, "conv_wgrad x2", x1.dtype)
+        C2 = x2.shape[3]
+    want = (B, H, W, n) if mode == CONV3 else (B, 2 * H, 2 * W, n)
+    if tuple(dy.shape) != want:
+        raise UiaError(f"conv_wgrad: dy {tuple(dy.shape)}, expected {want}")
+    rows, cols = (n, 9 * (C1 + C2)) if mode == CONV3 else (4 * n, C1)
+    S = lib().uia_conv_wgrad_splits(mode, B, H, W, C1, C2, n)
+    ws = torch.empty(S * rows * cols, device=x1.device, dtype=torch.float32) if S > 1 else None
+    dw = torch.empty(rows, cols, device=x1.device, dtype=torch.float32)
+    check(lib().uia_conv_wgrad(_stream(), _code(x1.dtype), mode, B, H, W, C1, C2, _p(x1), _p(x2), n, _p(dy), _p(ws), _p(dw)), "uia_conv_wgrad")
+    return dw
+
+
+def colsum_ordered(y):
+    """fp32 column sums of a contiguous [..., C] tensor in a fixed order (uia_colsum_ordered)."""
+    if not y.is_contiguous():
+        raise UiaError("colsum_ordered: contiguous rows required")
+    C = y.shape[-1]
+    M = y.numel() // C
+    ws = torch.empty(BN_SLICES * C * 3, device=y.device, dtype=torch.float32)
+    out = torch.empty(C, device=y.device, dtype=torch.float32)
+    check(lib().uia_colsum_ordered(_stream(), _code(y.dtype), M, C, _p(y), _p(ws), _p(out)), "uia_colsum_ordered")
+    return out
+
+
+def bn_fwd(y, gamma, beta, running_mean, running_var, num_batches_tracked, training, momentum=0.1, eps=1e-5, relu=True):
+    """BatchNorm2d (+ ReLU) on NHWC y (uia_bn_fwd).  Returns (out, mean, invstd, scale, shift); mean / invstd are None in eval mode.
+    Training updates running_mean / running_var / num_batches_tracked in place (any of them may be None: no update)."""
+    _nhwc(y, "bn_fwd y")
+    C = y.shape[3]
+    M = y.numel() // C
+    for t, nm in ((gamma, "gamma"), (beta, "beta"), (running_mean, "running_mean"), (running_var, "running_var")):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != C):
+            raise UiaError(f"bn_fwd: {nm} must be contiguous fp32 [{C}]")
+    if num_batches_tracked is not None and num_batches_tracked.dtype != torch.int64:
+        raise UiaError("bn_fwd: num_batches_tracked must be int64")
+    f = lambda: torch.empty(C, device=y.device, dtype=torch.float32)   # noqa: E731
+    scale, shift = f(), f()
+    mean, invstd, ws = (f(), f(), torch.empty(BN_SLICES * C * 3, device=y.device, dtype=torch.float32)) if training else (None, None, None)
+    out = torch.empty_like(y)
+    check(lib().uia_bn_fwd(_stream(), _code(y.dtype), int(bool(training)), M, C, _p(y), _p(gamma), _p(beta), _p(running_mean), _p(running_var),
+                           _p(num_batches_tracked), float(momentum), float(eps), _p(ws), _p(mean), _p(invstd), _p(scale), _p(shift), int(bool(relu)), _p(out)),
+          "uia_bn_fwd")
+    return out, mean, invstd, scale, shift
+
+
+def bn_relu_bwd(y, dout, scale, shift, mean, invstd, gamma):
+    """Backward of train-mode BatchNorm2d + ReLU (uia_bn_relu_bwd): returns (dy, dgamma, dbeta)."""
+    _nhwc(y, "bn_relu_bwd y")
+    _nhwc(dout, "bn_relu_bwd dout", y.dtype)
+    if dout.shape != y.shape:
+        raise UiaError("bn_relu_bwd: dout and y differ in shape")
+    C = y.shape[3]
+    for t, nm in ((scale, "scale"), (shift, "shift"), (mean, "mean"), (invstd, "invstd"), (gamma, "gamma")):
+        if t is None or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != C:
+            raise UiaError(f"bn_relu_bwd: {nm} must be contiguous fp32 [{C}]")
+    M = y.numel() // C
+    ws = torch.empty(BN_SLICES * C * 3, device=y.device, dtype=torch.float32)
+    dgamma = torch.empty(C, device=y.device, dtype=torch.float32)
+    dbeta = torch.empty(C, device=y.device, dtype=torch.float32)
+    dy = torch.empty_like(y)
+    check(lib().uia_bn_relu_bwd(_stream(), _code(y.dtype), M, C, _p(y), _p(dout), _p(scale), _p(shift), _p(mean), _p(invstd), _p(gamma), _p(ws),
+                                _p(dgamma), _p(dbeta), _p(dy)), "uia_bn_relu_bwd")
+    return dy, dgamma, dbeta
+
+
+def upsample_ac(x, f, backward=False):
+    """Bilinear upsample, align_corners=True, integer factor f, NHWC (uia_upsample_ac).  backward=True: x is dout [B,fH,fW,C] -> dx [B,H,W,C]."""
+    _nhwc(x, "upsample_ac")
+    B, H, W, C = x.shape
+    f = int(f)
+    if backward:
+        if H % f or W % f:
+            raise UiaError(f"upsample_ac: gradient grid {H}x{W} is not a multiple of {f}")
+        H, W = H // f, W // f
+        out = torch.empty(B, H, W, C, device=x.device, dtype=x.dtype)
+    else:
+        out = torch.empty(B, H * f, W * f, C, device=x.device, dtype=x.dtype)
+    check(lib().uia_upsample_ac(_stream(), _code(x.dtype), int(bool(backward)), B, H, W, C, f, _p(x), _p(out)), "uia_upsample_ac")
+    return out
+
+
+def resize_aa(x, size):
+    """Antialiased bicubic resize (align_corners=False) of NHWC x [B,Hi,Wi,C] to NCHW fp32 [B,C,Ho,Wo] (uia_resize_aa)."""
+    _nhwc(x, "resize_aa")
+    B, Hi, Wi, C = x.shape
+    Ho, Wo = size
+    tmp = torch.empty(B * C * Hi * Wo, device=x.device, dtype=torch.float32)
+    out = torch.empty(B, C, Ho, Wo, device=x.device, dtype=torch.float32)
+    check(lib().uia_resize_aa(_stream(), _code(x.dtype), 0, B, C, Hi, Wi, Ho, Wo, _p(x), _p(tmp), _p(out), None, None), "uia_resize_aa")
+    return out
+
+
+def resize_aa_bwd(dout, in_hw, dtype):
+    """Backward of resize_aa: dout fp32 NCHW [B,C,Ho,Wo] -> dx NHWC [B,Hi,Wi,C] in dtype."""
+    if dout.dim() != 4 or dout.dtype != torch.float32 or not dout.is_contiguous():
+        raise UiaError("resize_aa_bwd: dout must be contiguous fp32 [B, C, Ho, Wo]")
+    B, C, Ho, Wo = dout.shape
+    Hi, Wi = in_hw
+    tmp = torch.empty(B * C * Hi * Wo, device=dout.device, dtype=torch.float32)
+    dx = torch.empty(B, Hi, Wi, C, device=dout.device, dtype=dtype)
+    check(lib().uia_resize_aa(_stream(), _code(dtype), 1, B, C, Hi, Wi, Ho, Wo, None, _p(tmp), None, _p(dout), _p(dx)), "uia_resize_aa")
+    return dx
