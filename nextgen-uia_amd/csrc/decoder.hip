@@ -281,7 +281,7 @@ __global__ void im2col3x3_kernel(int B, int h, int w, int C, int ntok, int tok_o
         store4(cols + prow * 9 * C + (size_t)kk * C + c, v);
     }
 }
-// dx[b][tok_off + p][c] = Σ_kk dcols[(b, p - off(kk))][kk*C + c]   (gather form, no atomics); rows < tok_off are zeroed
+// dx[b][tok_off + p][c] = Σ_kk dcols[(b, p - off(kk))][kk*C + c]   (gather form, no atomics); rows outside the grid are zeroed
 template <typename T>
 __global__ void col2im3x3_kernel(int B, int h, int w, int C, int ntok, int tok_off, const T* __restrict__ dcols, float* __restrict__ dx) {
     const int C4 = C >> 2;
@@ -290,7 +290,7 @@ __global__ void col2im3x3_kernel(int B, int h, int w, int C, int ntok, int tok_o
         const int c = (int)(i % C4) * 4;
         const int tok = (int)((i / C4) % ntok), b = (int)(i / ((size_t)C4 * ntok));
         f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-        if (tok >= tok_off) {
+        if (tok >= tok_off && tok < tok_off + h * w) {                    // tokens past the grid (ntok > tok_off + h·w) are no pixel: zero
             const int pix = tok - tok_off, y = pix / w, xq = pix % w;
 #pragma unroll
             for (int kk = 0; kk < 9; ++kk) {
@@ -433,7 +433,7 @@ int uia_film_bwd_launch(hipStream_t stream, int B, int N, int C, const float* dy
 }
 
 int uia_im2col3x3_launch(hipStream_t stream, int dtype, int B, int h, int w, int C, int ntok, int tok_off, const float* x, void* cols) {
-    UIA_CHECK_ARG(B > 0 && h > 0 && w > 0 && C % 4 == 0 && ntok >= tok_off + h * w && x && cols, "uia_im2col3x3: bad arguments");
+    UIA_CHECK_ARG(B > 0 && h > 0 && w > 0 && C > 0 && C % 4 == 0 && tok_off >= 0 && ntok >= tok_off + h * w && x && cols, "uia_im2col3x3: bad arguments");
     const int g = grid_for((size_t)B * h * w * 9 * C / 4, 256);
     if (dtype == UIA_BF16) hipLaunchKernelGGL(im2col3x3_kernel<bf16_t>, dim3(g), dim3(256), 0, stream, B, h, w, C, ntok, tok_off, x, (bf16_t*)cols);
     else if (dtype == UIA_F32) hipLaunchKernelGGL(im2col3x3_kernel<float>, dim3(g), dim3(256), 0, stream, B, h, w, C, ntok, tok_off, x, (float*)cols);
@@ -442,7 +442,7 @@ int uia_im2col3x3_launch(hipStream_t stream, int dtype, int B, int h, int w, int
     return 0;
 }
 int uia_col2im3x3_launch(hipStream_t stream, int dtype, int B, int h, int w, int C, int ntok, int tok_off, const void* dcols, float* dx) {
-    UIA_CHECK_ARG(B > 0 && h > 0 && w > 0 && C % 4 == 0 && ntok >= tok_off + h * w && dcols && dx, "uia_col2im3x3: bad arguments");
+    UIA_CHECK_ARG(B > 0 && h > 0 && w > 0 && C > 0 && C % 4 == 0 && tok_off >= 0 && ntok >= tok_off + h * w && dcols && dx, "uia_col2im3x3: bad arguments");
     const int g = grid_for((size_t)B * ntok * C / 4, 256);
     if (dtype == UIA_BF16) hipLaunchKernelGGL(col2im3x3_kernel<bf16_t>, dim3(g), dim3(256), 0, stream, B, h, w, C, ntok, tok_off, (const bf16_t*)dcols, dx);
     else if (dtype == UIA_F32) hipLaunchKernelGGL(col2im3x3_kernel<float>, dim3(g), dim3(256), 0, stream, B, h, w, C, ntok, tok_off, (const float*)dcols, dx);

@@ -447,6 +447,32 @@ def _stream():
     return raw_stream()
 
 
+def _dense(t, name, dtypes, numel=None, align=1):
+    """Refuse (UiaError, before any launch) an operand that is not a contiguous tensor of one of `dtypes` with exactly `numel`
+    elements and a data pointer aligned to `align` bytes (the vector loads / stores of the kernel that reads it; "v4": four elements)."""
+    if not isinstance(t, torch.Tensor):
+        raise UiaError(f"{name}: a tensor is required, got {type(t).__name__}")
+    if t.dtype not in dtypes:
+        raise UiaError(f"{name}: dtype {t.dtype}, expected {' or '.join(str(d) for d in dtypes)}")
+    if not t.is_contiguous():
+        raise UiaError(f"{name}: must be contiguous (shape {tuple(t.shape)}, stride {t.stride()})")
+    if numel is not None and t.numel() != numel:
+        raise UiaError(f"{name}: {t.numel()} elements (shape {tuple(t.shape)}), expected {numel}")
+    if align == "v4":
+        align = 4 * t.element_size()
+    if t.data_ptr() % align:
+        raise UiaError(f"{name}: data pointer not aligned to {align} bytes")
+    return t
+
+
+def _require(cond, msg):
+    if not cond:
+        raise UiaError(msg)
+
+
+_F32, _FT = (torch.float32,), (torch.bfloat16, torch.float32)
+
+
 def _rowmajor(t, name):
     if t.dim() != 2 or t.stride(1) != 1:
         raise UiaError(f"{name} must be a 2-D row-major tensor (got shape {tuple(t.shape)}, stride {t.stride()})")
@@ -937,13 +963,16 @@ def layernorm_bwd(dy, x, gamma, eps, dres=None, dx32=None, dx_t=None, rows=None,
 
 
 def cast(src, dst, scale=1.0):
-    assert src.dtype == torch.float32 and src.is_contiguous() and dst.is_contiguous() and src.numel() == dst.numel()
+    _dense(src, "cast: src", _F32, align=16)
+    _dense(dst, "cast: dst", _FT, src.numel(), align="v4")
     check(lib().uia_cast(_stream(), _code(dst.dtype), src.numel(), _p(src), _p(dst), scale), "uia_cast")
 
 
 def transpose_cast(src, dst):
-    assert src.dtype == torch.float32 and src.dim() == 2 and src.is_contiguous() and dst.is_contiguous()
-    assert tuple(dst.shape) == (src.shape[1], src.shape[0])
+    _dense(src, "transpose_cast: src", _F32)
+    _dense(dst, "transpose_cast: dst", _FT)
+    _require(src.dim() == 2 and tuple(dst.shape) == (src.shape[1], src.shape[0]),
+             f"transpose_cast: dst shape {tuple(dst.shape)} is not the transpose of src {tuple(src.shape)}")
     check(lib().uia_transpose_cast(_stream(), _code(dst.dtype), src.shape[0], src.shape[1], _p(src), _p(dst)), "uia_transpose_cast")
 
 
@@ -970,6 +999,13 @@ def pack_table(entries, device):
             elif t is not None:
                 assert t.is_contiguous() and t.numel() == RP * CP and t.device == src.device
                 setattr(d, name, _p(t))
+            if t is not None and name.endswith("_kb"):
+                # a K-blocked form writes whole 64-byte groups along its K extent (cols for row_kb, rows for tr_kb): a padded extent that is
+                # not a multiple of the group would put the last group past the destination
+                g = 64 // (t.view.element_size() if isinstance(t, RawDest) else t.element_size())
+                k, kp = (Cc, CP) if name == "row_kb" else (R, RP)
+                if -(-k // g) * g > kp:
+                    raise UiaError(f"pack_table: {name} needs its K extent {kp} >= {k} rounded up to {g}")
         max_elems = max(max_elems, R * Cc)
     nbytes = C.sizeof(arr)
     dev = torch.device(device)
@@ -998,14 +1034,21 @@ def pack_table(entries, device):
 
 
 def pack_weights(table, n, max_elems, dtype):
+    _dense(table, "pack_weights: table", (torch.uint8,), align=8)
+    _require(table.is_cuda and table.numel() >= n * C.sizeof(PackDesc), f"pack_weights: a device table of {n} descriptors is required")
     check(lib().uia_pack_weights(_stream(), _code(dtype), n, _p(table), max_elems), "uia_pack_weights")
 
 
 def im2col(img, out, patch):
     """out [B*gh*gw, ld]: ld == C*patch^2 with patch % 4 == 0 takes the vectorised kernel, anything else the padded one
     (columns beyond C*patch^2 are zero-filled, e.g. ViT-L/14: 588 -> 640 for the GEMM's K granule)."""
+    _require(img.dim() == 4 and out.dim() == 2, "im2col: img [B, C, H, W] and out [rows, ld] are required")
     B, Cc, H, W = img.shape
-    assert img.dtype == torch.float32 and img.is_contiguous() and out.is_contiguous()
+    _require(H % patch == 0 and W % patch == 0, f"im2col: {H}x{W} image is not a whole number of {patch}-pixel patches")
+    _dense(img, "im2col: img", _F32, align=16)
+    _dense(out, "im2col: out", _FT)
+    _require(out.shape[0] == B * (H // patch) * (W // patch) and out.shape[1] >= Cc * patch * patch,
+             f"im2col: out shape {tuple(out.shape)}, expected [{B * (H // patch) * (W // patch)}, >= {Cc * patch * patch}]")
     if patch % 4 == 0 and out.shape[1] == Cc * patch * patch and W % 4 == 0:
         check(lib().uia_im2col(_stream(), _code(out.dtype), B, Cc, H, W, patch, _p(img), _p(out)), "uia_im2col")
     else:
@@ -1013,31 +1056,57 @@ def im2col(img, out, patch):
 
 
 def fill_cls(x, cls, pos0):
+    _require(x.dim() == 3, "fill_cls: x [B, N, D] is required")
     B, N, D = x.shape
+    _dense(x, "fill_cls: x", _F32)
+    _dense(cls, "fill_cls: cls", _F32, D)
+    if pos0 is not None:
+        _dense(pos0, "fill_cls: pos0", _F32, D)
     check(lib().uia_fill_cls(_stream(), B, N, D, _p(cls), _p(pos0), _p(x)), "uia_fill_cls")
+
+
+def _embed_tables(what, table, pos, type0, out, rows):
+    _require(table.dim() == 2 and pos.dim() == 2 and pos.shape[1] == table.shape[1] and table.shape[1] % 4 == 0,
+             f"{what}: table [V, D] and pos [P, D] with D % 4 == 0 are required, got {tuple(table.shape)} and {tuple(pos.shape)}")
+    D = table.shape[1]
+    _dense(table, f"{what}: table", _F32, align=16)
+    _dense(pos, f"{what}: pos", _F32, align=16)
+    if type0 is not None:
+        _dense(type0, f"{what}: type0", _F32, D, align=16)
+    _dense(out, f"{what}: out", _F32, rows * D, align=16)
 
 
 def embed(ids, table, pos, type0, out):
     rows, L = ids.numel(), ids.shape[-1]
-    assert ids.dtype == torch.int64 and ids.is_contiguous()
+    _dense(ids, "embed: ids", (torch.int64,))
+    _embed_tables("embed", table, pos, type0, out, rows)
     check(lib().uia_embed(_stream(), rows, L, table.shape[1], table.shape[0], pos.shape[0], _p(ids), _p(table), _p(pos), _p(type0), _p(out)), "uia_embed")
 
 
 def embed_packed(ids, pos_idx, table, pos, type0, out):
     """out[r] = table[ids[r]] + pos[pos_idx[r]] + type0 for the packed (valid) tokens r."""
-    assert ids.dtype == pos_idx.dtype == torch.int64 and ids.is_contiguous() and pos_idx.is_contiguous() and ids.numel() == pos_idx.numel() == out.shape[0]
+    _dense(ids, "embed_packed: ids", (torch.int64,))
+    _dense(pos_idx, "embed_packed: pos_idx", (torch.int64,), ids.numel())
+    _embed_tables("embed_packed", table, pos, type0, out, ids.numel())
     check(lib().uia_embed_packed(_stream(), ids.numel(), out.shape[1], table.shape[0], pos.shape[0], _p(ids), _p(pos_idx), _p(table), _p(pos), _p(type0), _p(out)),
           "uia_embed_packed")
 
 
 def embed_bwd(ids, dx, dtable, pad_id=-1):
     """dtable[ids[r]] += dx[r] for every row r with ids[r] != pad_id (dtable fp32, caller-zeroed or accumulating)."""
-    assert ids.dtype == torch.int64 and ids.is_contiguous() and dx.dtype == dtable.dtype == torch.float32 and dx.is_contiguous() and dtable.is_contiguous()
+    _dense(ids, "embed_bwd: ids", (torch.int64,))
+    _require(dx.dim() >= 1 and dtable.dim() == 2 and dx.shape[-1] == dtable.shape[1], "embed_bwd: dx [.., D] and dtable [V, D] are required")
+    _dense(dx, "embed_bwd: dx", _F32, ids.numel() * dtable.shape[1])
+    _dense(dtable, "embed_bwd: dtable", _F32)
     check(lib().uia_embed_bwd(_stream(), ids.numel(), dx.shape[-1], dtable.shape[0], _p(ids), _p(dx), _p(dtable), pad_id), "uia_embed_bwd")
 
 
 def gather_rows(src, idx, dst):
-    assert idx.dtype == torch.int64
+    """dst[i] = src[idx[i]]; idx must lie in [0, src rows): the kernel reads it unchecked."""
+    _dense(idx, "gather_rows: idx", (torch.int64,))
+    _require(src.dim() >= 1 and src.shape[-1] % 4 == 0, "gather_rows: src [.., D] with D % 4 == 0 is required")
+    _dense(src, "gather_rows: src", _F32, align=16)
+    _dense(dst, "gather_rows: dst", _F32, idx.numel() * src.shape[-1], align=16)
     check(lib().uia_gather_rows(_stream(), idx.numel(), src.shape[-1], _p(src), _p(idx), _p(dst)), "uia_gather_rows")
 
 
@@ -1334,47 +1403,91 @@ def lora_rank_update(q_all, ws, out, alpha, drop_p=0.0, seeds=()):
 
 
 def colsum(a, out):
-    lda = _rowmajor(a, "a")
-    assert out.dtype == torch.float32 and out.numel() == a.shape[1]
+    lda = _rowmajor(a, "colsum: a")
+    _require(a.dtype in _FT, f"colsum: a dtype {a.dtype}, expected bf16 or fp32")
+    _dense(out, "colsum: out", _F32, a.shape[1])
     check(lib().uia_colsum(_stream(), _code(a.dtype), a.shape[0], a.shape[1], _p(a), lda, _p(out)), "uia_colsum")
 
 
 # ------------------------------------------------------------------------------------------- CLIPSeg decoder pieces
 def layernorm_bwd_affine(dy, x, gamma, eps, dx32, g_gamma, g_beta, dres=None):
-    D = gamma.numel()
+    """dx32 = LayerNorm backward of the fp32 rows x (+ dres); dγ, dβ are ADDED into g_gamma / g_beta.  dy in T (bf16 or fp32)."""
+    D = _dense(gamma, "layernorm_bwd_affine: gamma", _F32, align=16).numel()
+    _dense(dy, "layernorm_bwd_affine: dy", _FT, align="v4")
+    _require(D > 0 and dy.numel() % D == 0, f"layernorm_bwd_affine: dy has {dy.numel()} elements, not a whole number of rows of D = {D}")
+    for name, t in (("x", x), ("dx32", dx32), ("dres", dres)):
+        if t is not None or name != "dres":
+            _dense(t, f"layernorm_bwd_affine: {name}", _F32, dy.numel(), align=16)
+    for name, t in (("g_gamma", g_gamma), ("g_beta", g_beta)):
+        _dense(t, f"layernorm_bwd_affine: {name}", _F32, D, align=16)
     check(lib().uia_layernorm_bwd_affine(_stream(), _code(dy.dtype), dy.numel() // D, D, _p(dy), _p(x), _p(gamma), eps, _p(dres), _p(dx32), _p(g_gamma), _p(g_beta)),
           "uia_layernorm_bwd_affine")
 
 
 def film_fwd(x, mul, add, y):
+    _require(x.dim() == 3, "film_fwd: x [B, N, C] is required")
     B, N, Cc = x.shape
+    _dense(x, "film_fwd: x", _F32, align=16)
+    _dense(mul, "film_fwd: mul", _F32, B * Cc, align=16)
+    _dense(add, "film_fwd: add", _F32, B * Cc, align=16)
+    _dense(y, "film_fwd: y", _F32, x.numel(), align=16)
     check(lib().uia_film_fwd(_stream(), B, N, Cc, _p(x), _p(mul), _p(add), _p(y)), "uia_film_fwd")
 
 
 def film_bwd(dy, x, mul, dx, dmul, dadd):
+    _require(x.dim() == 3, "film_bwd: x [B, N, C] is required")
     B, N, Cc = x.shape
+    for name, t, n in (("dy", dy, x.numel()), ("x", x, None), ("dx", dx, x.numel()), ("mul", mul, B * Cc), ("dmul", dmul, B * Cc), ("dadd", dadd, B * Cc)):
+        _dense(t, f"film_bwd: {name}", _F32, n)
     check(lib().uia_film_bwd(_stream(), B, N, Cc, _p(dy), _p(x), _p(mul), _p(dx), _p(dmul), _p(dadd)), "uia_film_bwd")
 
 
 def im2col3x3(x, cols, h, w, tok_off=1):
+    _require(x.dim() == 3, "im2col3x3: x [B, ntok, C] is required")
     B, N, Cc = x.shape
+    _require(0 <= tok_off and tok_off + h * w <= N, f"im2col3x3: tokens {tok_off} .. {tok_off + h * w} outside the {N} rows of x")
+    _dense(x, "im2col3x3: x", _F32, align=16)
+    _dense(cols, "im2col3x3: cols", _FT, B * h * w * 9 * Cc, align="v4")
     check(lib().uia_im2col3x3(_stream(), _code(cols.dtype), B, h, w, Cc, N, tok_off, _p(x), _p(cols)), "uia_im2col3x3")
 
 
 def col2im3x3(dcols, dx, h, w, tok_off=1):
+    _require(dx.dim() == 3, "col2im3x3: dx [B, ntok, C] is required")
     B, N, Cc = dx.shape
+    _require(0 <= tok_off and tok_off + h * w <= N, f"col2im3x3: tokens {tok_off} .. {tok_off + h * w} outside the {N} rows of dx")
+    _dense(dx, "col2im3x3: dx", _F32, align=16)
+    _dense(dcols, "col2im3x3: dcols", _FT, B * h * w * 9 * Cc, align="v4")
     check(lib().uia_col2im3x3(_stream(), _code(dcols.dtype), B, h, w, Cc, N, tok_off, _p(dcols), _p(dx)), "uia_col2im3x3")
 
 
+def _shuffle_rows(what, tmp, B, h, w, k1, k2):
+    ld = _rowmajor(tmp, f"{what}: tmp")
+    _require(tmp.dtype in _FT, f"{what}: tmp dtype {tmp.dtype}, expected bf16 or fp32")
+    _require(tmp.shape[0] == B * h * w * k1 * k1 and tmp.shape[1] >= k2 * k2,
+             f"{what}: tmp shape {tuple(tmp.shape)}, expected [{B * h * w * k1 * k1}, >= {k2 * k2}]")
+    return ld
+
+
 def unshuffle(tmp, out, B, h, w, k1, k2, bias=0.0):
+    _shuffle_rows("unshuffle", tmp, B, h, w, k1, k2)
+    _dense(out, "unshuffle: out", _F32, B * h * w * (k1 * k2) ** 2)
     check(lib().uia_unshuffle(_stream(), _code(tmp.dtype), B, h, w, k1, k2, _p(tmp), tmp.stride(0), bias, _p(out)), "uia_unshuffle")
 
 
 def shuffle(dout, dtmp, B, h, w, k1, k2):
+    """dtmp [B·h·w·k1², ld]: every column is written, the ones beyond k2² with zeros, so dtmp must be contiguous (ld = its width)."""
+    _shuffle_rows("shuffle", dtmp, B, h, w, k1, k2)
+    _dense(dtmp, "shuffle: dtmp", _FT)
+    _dense(dout, "shuffle: dout", _F32, B * h * w * (k1 * k2) ** 2)
     check(lib().uia_shuffle(_stream(), _code(dtmp.dtype), B, h, w, k1, k2, _p(dout), _p(dtmp), dtmp.stride(0)), "uia_shuffle")
 
 
 def act_bwd(dy, y, act, out):
+    """out = dy · act'(y) elementwise; y is the post-activation for ReLU, the pre-activation for GELU / QuickGELU."""
+    _require(act in _ACT, f"act_bwd: unknown activation {act!r}")
+    _dense(dy, "act_bwd: dy", _FT)
+    _dense(y, "act_bwd: y", (dy.dtype,), dy.numel())
+    _dense(out, "act_bwd: out", (dy.dtype,), dy.numel())
     check(lib().uia_act_bwd(_stream(), _code(dy.dtype), dy.numel(), _p(dy), _p(y), _ACT[act], _p(out)), "uia_act_bwd")
 
 
@@ -1382,9 +1495,12 @@ def act_bwd(dy, y, act, out):
 def upsample_bilinear(src, B, C, h, w, H, W, dst, backward=False):
     """forward: src token-major fp32 [B*h*w, ld>=C] -> dst [B,C,H,W]; backward: src = d(dst) [B,C,H,W] -> dst token-major (overwritten)."""
     tok = dst if backward else src
-    assert tok.dtype == torch.float32 and tok.dim() == 2 and tok.stride(1) == 1 and tok.shape[0] == B * h * w and tok.shape[1] >= C
+    _rowmajor(tok, "upsample_bilinear: token rows")
+    _require(tok.dtype == torch.float32 and tok.shape[0] == B * h * w and tok.shape[1] >= C,
+             f"upsample_bilinear: token rows {tuple(tok.shape)} {tok.dtype}, expected fp32 [{B * h * w}, >= {C}]")
     img = src if backward else dst
-    assert img.dtype == torch.float32 and img.is_contiguous() and tuple(img.shape) == (B, C, H, W)
+    _dense(img, "upsample_bilinear: image", _F32, B * C * H * W)
+    _require(tuple(img.shape) == (B, C, H, W), f"upsample_bilinear: image shape {tuple(img.shape)}, expected {(B, C, H, W)}")
     if backward:
         check(lib().uia_upsample_bilinear_bwd(_stream(), B, C, h, w, H, W, _p(src), _p(dst), dst.stride(0)), "uia_upsample_bilinear_bwd")
     else:
@@ -1395,22 +1511,31 @@ def segment_mean(x, B, n, out, backward=False):
     """forward: x fp32 [B*n, C] -> out [B, C] (mean over each image's n tokens); backward: x = d(out) [B, C] -> out [B*n, C]."""
     tok = out if backward else x
     vec = x if backward else out
+    _rowmajor(tok, "segment_mean: token rows")
+    _require(vec.dim() == 2, "segment_mean: [B, C] is required")
     Cc = vec.shape[1]
-    assert tok.dtype == vec.dtype == torch.float32 and tok.stride(1) == 1 and vec.is_contiguous() and tok.shape[0] == B * n and tok.shape[1] == Cc
+    _dense(vec, "segment_mean: [B, C]", _F32, B * Cc)
+    _require(tok.dtype == torch.float32 and tok.shape[0] == B * n and tok.shape[1] == Cc,
+             f"segment_mean: token rows {tuple(tok.shape)} {tok.dtype}, expected fp32 [{B * n}, {Cc}]")
     if backward:
         check(lib().uia_segment_mean_bwd(_stream(), B, n, Cc, _p(x), _p(out), out.stride(0)), "uia_segment_mean_bwd")
     else:
         check(lib().uia_segment_mean_fwd(_stream(), B, n, Cc, _p(x), x.stride(0), _p(out)), "uia_segment_mean_fwd")
 
 
-def dicece_fwd_bwd(logits, label, smooth_nr=1e-8, smooth_dr=1e-8):
-    """logits fp32 [B,C,H,W], label [B,1,H,W] (class indices) -> (loss 0-dim fp32, dlogits fp32 [B,C,H,W])."""
-    assert logits.dtype == torch.float32 and logits.is_contiguous() and logits.dim() == 4
+def dicece_fwd_bwd(logits, label, smooth_nr=1e-8, smooth_dr=1e-8, out=None):
+    """logits fp32 [B,C,H,W], label [B,1,H,W] (class indices) -> (loss 0-dim fp32, dlogits fp32 [B,C,H,W]).
+    out: an optional (loss, dlogits) pair of fp32 tensors (1 and B·C·H·W elements) to write into instead of new ones."""
+    _require(logits.dim() == 4, "dicece_fwd_bwd: logits [B, C, H, W] are required")
+    _dense(logits, "dicece_fwd_bwd: logits", _F32)
     B, Cc, H, W = logits.shape
+    _require(label.numel() == B * H * W, f"dicece_fwd_bwd: label has {label.numel()} elements, expected {B * H * W}")
     lab = label.reshape(B, H * W).to(torch.float32).contiguous()
     ws = torch.empty(lib().uia_dicece_workspace_bytes(B) // 4, device=logits.device, dtype=torch.float32)
-    loss = torch.empty((), device=logits.device, dtype=torch.float32)
-    dl = torch.empty_like(logits)
+    if out is None:
+        loss, dl = torch.empty((), device=logits.device, dtype=torch.float32), torch.empty_like(logits)
+    else:
+        loss, dl = _dense(out[0], "dicece_fwd_bwd: loss", _F32, 1), _dense(out[1], "dicece_fwd_bwd: dlogits", _F32, logits.numel())
     check(lib().uia_dicece_fwd_bwd(_stream(), B, Cc, H * W, _p(logits), _p(lab), smooth_nr, smooth_dr, _p(ws), _p(loss), _p(dl)), "uia_dicece_fwd_bwd")
     return loss, dl
 
