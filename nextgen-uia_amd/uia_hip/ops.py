@@ -5,6 +5,7 @@ CPU path: CPU tensors raise.  `dtype` of an op is taken from its operand tensors
 (torch.bfloat16 -> UIA_BF16, torch.float32 -> UIA_F32).
 """
 import ctypes as C
+from typing import NamedTuple
 
 import torch
 
@@ -228,14 +229,14 @@ KBLOCK_ACT = True        # GEMM -> GEMM activations travel K-blocked ([K/g][rows
 
 
 def kb_group(dt):
-    return 64 // torch.empty(0, dtype=dt).element_size()
+    return 64 // dt.itemsize
 
 
 def kb_ok(M, N_consumer, K, dt):
     """May an [M, K] activation that ONE GEMM epilogue writes and ONE GEMM (N_consumer columns) reads travel K-blocked?  Both launches
     must land on a ring tile config with 64-byte sub-tiles (M > 2048 and more than 64 columns on either side)."""
-    return (KBLOCK_ACT and K % kb_group(dt) == 0 and K > 64 and auto_tile_cfg(M, N_consumer, K, torch.empty(0, dtype=dt).element_size()) in (8, 14)
-            and auto_tile_cfg(M, K, 128, torch.empty(0, dtype=dt).element_size()) == 8)
+    return (KBLOCK_ACT and K % kb_group(dt) == 0 and K > 64 and auto_tile_cfg(M, N_consumer, K, dt.itemsize) in (8, 14)
+            and auto_tile_cfg(M, K, 128, dt.itemsize) == 8)
 
 
 class KBlocked:
@@ -479,14 +480,123 @@ def _rowmajor(t, name):
     return t.stride(0)
 
 
+class Launch(NamedTuple):
+    """One uia_gemm call of a planned gemm(): rows [lo, hi) of the problem."""
+    lo: int
+    hi: int
+    tile_cfg: int       # the word uia_gemm receives: tile config (0 = the launcher's own choice) | rows per tile-order group << 8 | K slices << 16 | split-K phase << 22
+    base: int           # the tile config the schedule counts on: tile_cfg's where it names one, else the mirror of the launcher's choice (auto_tile_cfg, 23)
+    w_kblocked: bool    # the weight goes K-blocked
+    side: bool          # enqueued on the side stream, beside the launches that are not (_TailFork)
+    scratch: int        # fp32 elements of split-K scratch the launch works in (0: none)
+
+
+def plan_gemm(M, N, K, esz, ncu, tile_cfg=0, *, whole=False, ext=False, packed=False, on_device=True, out_group=0, resid_mod=0, drop=None, alpha=1.0,
+              a_kb=False, out_t_kb=False, act=False, aux_out=False, out_t=False, out32=False, resid=False, resid_t=False, rowsum=False, ln=False):
+    """The uia_gemm launches of one gemm() call, in enqueue order: pure host logic over plain values and the module's knobs (no device, no tensor).
+
+    M, N, K (an ExtW's whole K), esz = element size, ncu = compute units, tile_cfg = the caller's word.  Facts about the call: ext / packed = the weight is
+    an ExtW / a PackedW; on_device; out_group, resid_mod, alpha as given; drop = None | "a" | "acc"; a_kb / out_t_kb = `a` / `out_t` travel K-blocked;
+    act = act or dact given; ln = lnfold or resid_ln given; the rest = that operand is given.  whole = True plans what a direct _gemm_one call asks for:
+    one launch of all rows on `tile_cfg`, none of the splitting below.
+
+    With the launcher's own tile choice (tile_cfg == 0) the M tail of a launch whose last round of 256 x 256 tiles would leave most CUs idle goes through a
+    launch of its own on half-height tiles (tail_split_rows; cfg 13), split over K in two phases when it is a few tiles with a long K chain (tail_k_slices),
+    and beside the main launch (side stream, enqueued first) when it is small (small_tail), else behind it — or the whole launch moves to half-height
+    tiles, two workgroups per CU (cfg 14)."""
+    auto = 0 if (ext or tile_cfg & 255) else auto_tile_cfg(M, N, K, esz)
+
+    def launch(lo, hi, word, side=False, scratch=0):
+        base = word & 255
+        if ext:
+            if not base:            # W exists K-blocked only: ring tiles
+                base = 8 if hi - lo > 2048 else 13
+                word |= base
+        elif not base:
+            base = auto
+            # mirror of wide64_ok() in csrc/gemm.hip: the K = 64 read-modify-write stream (LoRA rank update / its data gradient) takes row-major W
+            if (base == 14 and esz == 2 and K == 64 and N % 64 == 0 and N * 144 <= 160 * 1024 and not (a_kb or out_t_kb or act or aux_out or rowsum or ln)
+                    and out_group == 0 and resid_mod == 0 and drop in (None, "acc")
+                    and ((out_t and not out32 and not resid and (resid_t or drop is not None)) or (out32 and not out_t and not resid_t and (resid or drop is not None)))):
+                base = 23
+            elif base == 8:
+                base = big_tile_cfg(N, K, esz)
+                word |= base
+        if PERSIST_STORE_ONLY and base == 8 and not (resid or resid_t or out32 or rowsum) and out_group == 0 and alpha == 1.0 and K * esz >= 1024:
+            base, word = 12, (word & ~255) | 12
+        if TILE_GROUP and N in TILE_GROUP and (word >> 8) == 0 and base in RING_CFGS:
+            word |= int(TILE_GROUP[N]) << 8
+        return Launch(lo, hi, word, base, bool(ext or (packed and KBLOCK_W and base in RING_CFGS and on_device)), side, scratch)
+
+    m_main = M
+    if whole or not on_device:
+        pass
+    elif ext:
+        if TAIL_SPLIT and tile_cfg == 0 and M > 2048:
+            m_main = tail_split_rows(M, N, ncu)
+    else:
+        if not K64_CFG14 and tile_cfg == 0 and auto == 14:
+            tile_cfg = 8
+        if TAIL_SPLIT and tile_cfg == 0 and out_group == 0 and resid_mod == 0 and drop is None and auto == 8:
+            m_main = tail_split_rows(M, N, ncu)
+            if SHORT_K_WIDE_HALF_N and N >= SHORT_K_WIDE_HALF_N and K * esz <= SHORT_K_WIDE_HALF_BYTES and esz == 2 and (SHORT_K_WIDE_HALF_STASH or not aux_out):
+                # short K loop, wide N (fc1 and its GELU' data gradient: K = 768, N = 3072): a quarter of a 256 x 256 launch is prologue + epilogue + hand-over that
+                # nothing overlaps (profiles/r04_d); on half-height tiles two workgroups share a CU and one's seam runs beside the other's K loop:
+                # 385 -> 338 us at M = 65 536, 266 -> 252 at 50 432 in isolation (bias + GELU store), level at N = 2304
+                tile_cfg, m_main = 14, M
+            if (m_main < M or HALF_HEIGHT_SHORT_K_ALWAYS) and HALF_HEIGHT_SHORT_K and CHAINS <= 1 and N <= 768 and K * esz <= 1536:      # (with other chains beside it a ragged round costs nothing: 40.99 -> 40.73 ms without this rule there)
+                # short K loops with a ragged last round (the image tower's output projection and its data gradient: 591 tiles on 256 CUs): the whole
+                # launch on half-height tiles, two workgroups per CU (tile cfg 14), instead of a main launch + a half-height tail launch — 1182 half
+                # tiles pack 2.31 rounds of 512, and one workgroup's epilogue runs beside its neighbour's K loop (round 3, isolated: 64 vs 62 + 21 us
+                # for the plain data gradient, 92 vs 102 us per 43 520 rows for the fp32-residual producer).  Longer K loops lose on it.
+                tile_cfg, m_main = 14, M
+    if m_main == M:
+        return [launch(0, M, tile_cfg)]
+    side = small_tail(M - m_main, N, ncu)
+    if CHAINS > 1 and not side and not ext:
+        # several independent chains of launches share the chip (engine.contrastive_step: the image tower in two slices beside the text tower): a ragged last
+        # round is filled by the other chains' workgroups, and a tail launch BEHIND the main one only adds a launch (40.87 -> 40.70 ms).  Small tails still
+        # fork to the side stream: without that split the ViT-L/14 + LoRA step loses 2.4 ms (a handful of tiles as a whole extra round).
+        return [launch(0, M, tile_cfg)]
+    slices = 0 if ext else tail_k_slices(M - m_main, N, K, esz, ncu)
+    if slices:      # two phases: slice partials into the scratch, then sum + epilogue
+        floats = -(-(M - m_main) // 128) * -(-N // 256) * 128 * 256
+        tail = [launch(m_main, M, 13 | slices << 16 | phase << 22, side, floats) for phase in (1, 2)]
+    else:
+        tail = [launch(m_main, M, 13, side)]
+    main = launch(0, m_main, 8 if ext else big_tile_cfg(N, K, esz))
+    return tail + [main] if side else [main] + tail
+
+
+def _plan_facts(a, w, act, dact, aux_out, out_group, resid_mod, drop, alpha, out_t, out32, resid, resid_t, rowsum, lnfold, resid_ln):
+    """plan_gemm's keywords about a gemm() / _gemm_one() call"""
+    return dict(ext=isinstance(w, ExtW), packed=isinstance(w, PackedW), on_device=a.is_cuda, out_group=out_group, resid_mod=resid_mod,
+                drop=None if drop is None else drop[0], alpha=alpha, a_kb=is_kb(a), out_t_kb=is_kb(out_t), act=act is not None or dact is not None,
+                aux_out=aux_out is not None, out_t=out_t is not None, out32=out32 is not None, resid=resid is not None, resid_t=resid_t is not None,
+                rowsum=rowsum is not None, ln=lnfold is not None or resid_ln is not None)
+
+
+def _cut(t, lo, hi, heads=1):
+    """Rows [lo, hi) of a row-indexed gemm() operand: a tensor [M, ·] (an ExtW's grouped a2: [G, M, K2]), a
+    KBlocked, None, or a tuple whose first `heads` elements are such operands and whose rest are parameters: (stats, …), (sums, …), (t2, group_cols);
+    resid3 = (hi plane, low bytes) has two."""
+    if t is None:
+        return None
+    if isinstance(t, tuple):
+        return tuple(_cut(x, lo, hi) for x in t[:heads]) + tuple(t[heads:])
+    if is_kb(t):
+        return t.row_range(lo, hi)
+    return t[lo:hi] if t.dim() < 3 else t[:, lo:hi]
+
+
 def gemm(a, w, *, bias=None, act=None, dact=None, aux_in=None, aux_out=None, resid=None, resid_mod=0, resid_row_off=0,
          resid_t=None, out_group=0, out_t=None, out32=None, alpha=1.0, tile_cfg=0, resid_ln=None, rowsum=None, lnfold=None, drop=None, a2=None,
          resid3=None, out_lo=None):
     """C = epilogue(alpha * a @ w.T).  a [M,K], w [N,K] (tensor or PackedW) share a dtype (bf16 | fp32); see include/uia_hip.h.
 
-    Host-side scheduling on top of uia_gemm (results do not depend on it): with the automatic tile choice, a weight that came
-    as a PackedW is handed to the ring kernels K-blocked, and the M tail of a launch whose last round of tiles would leave most
-    CUs idle goes through a second launch with half-height tiles (tail_split_rows).
+    Host-side scheduling on top of uia_gemm (results do not depend on it): plan_gemm() says which launches the call becomes — with the automatic
+    tile choice, a weight that came as a PackedW is handed to the ring kernels K-blocked, and the M tail of a launch whose last round of tiles would
+    leave most CUs idle goes through a launch of its own on half-height tiles; this function cuts the operands and enqueues them.
     resid_ln = (stats [M, 2], ln_weight, ln_bias): `resid` is the INPUT of a LayerNorm whose output is the residual to add; a fourth and
     fifth element (dim, eps) say that `stats` holds the row sums (Σ, Σ²) a producing GEMM left through `rowsum`, not (mean, rstd).
     drop = ("a", p, seed[, a_drop_out]): LoRA input dropout applied to `a` in flight (N = 64 stream kernel only; a_drop_out receives the dropped
@@ -503,92 +613,64 @@ def gemm(a, w, *, bias=None, act=None, dact=None, aux_in=None, aux_out=None, res
         if a2 is None or is_kb(a) or a.dtype != torch.bfloat16 or a.shape[1] != w.K - w.K2 or resid_mod or out_group or drop is not None:
             raise UiaError("gemm: an ExtW weight needs a2 = (t, group_cols), a row-major bf16 `a` of K - K2 columns and a plain epilogue")
         t2, gcols = a2
-        M = a.shape[0]
+        M, N, K = a.shape[0], w.N, w.K
         if t2.dtype != a.dtype or t2.shape[-1] != w.K2 or t2.shape[-2] != M or t2.stride(-1) != 1 or t2.stride(-2) != w.K2 or (t2.dim() == 3 and t2.shape[0] * gcols != w.N):
             raise UiaError(f"gemm: a2 operand {tuple(t2.shape)} does not match [groups, {M}, {w.K2}] with {w.N} columns in groups of {gcols}")
-        m_main = tail_split_rows(M, w.N, num_cus(a.device.index)) if (TAIL_SPLIT and tile_cfg == 0 and M > 2048) else M
-        cut = lambda t, lo, hi: None if t is None else t[lo:hi]
-        def part(lo, hi, cfg):
-            _gemm_one(a[lo:hi], w, bias=bias, act=act, dact=dact, aux_in=cut(aux_in, lo, hi), aux_out=cut(aux_out, lo, hi), resid=cut(resid, lo, hi),
-                      resid_t=cut(resid_t, lo, hi), out_t=cut(out_t, lo, hi), out32=cut(out32, lo, hi), alpha=alpha, tile_cfg=cfg,
-                      resid_ln=None if resid_ln is None else (resid_ln[0][lo:hi],) + tuple(resid_ln[1:]), rowsum=cut(rowsum, lo, hi),
-                      lnfold=None if lnfold is None else (lnfold[0][lo:hi],) + tuple(lnfold[1:]), a2=(t2[..., lo:hi, :], gcols))
-        if m_main >= M:
-            part(0, M, tile_cfg or (8 if M > 2048 else 13))
-        elif a.is_cuda and small_tail(M - m_main, w.N, num_cus(a.device.index)):
-            fork = _TailFork(a.device)
-            with fork:
-                part(m_main, M, 13)
-            part(0, m_main, 8)
-            fork.join()
-        else:
-            part(0, m_main, 8)
-            part(m_main, M, 13)
+    else:
+        M, (N, K) = (a.rows if is_kb(a) else a.shape[0]), (w.row if isinstance(w, PackedW) else w).shape
+    plan = plan_gemm(M, N, K, a.element_size(), num_cus(a.device.index) if a.is_cuda else 0, tile_cfg,
+                     **_plan_facts(a, w, act, dact, aux_out, out_group, resid_mod, drop, alpha, out_t, out32, resid, resid_t, rowsum, lnfold, resid_ln))
+    if len(plan) == 1:      # all rows at once: the operands pass as they came (row-remapped ones are not [M, ·])
+        _gemm_one(a, w, bias=bias, act=act, dact=dact, aux_in=aux_in, aux_out=aux_out, resid=resid, resid_mod=resid_mod, resid_row_off=resid_row_off,
+                  resid_t=resid_t, out_group=out_group, out_t=out_t, out32=out32, alpha=alpha, resid_ln=resid_ln, rowsum=rowsum, lnfold=lnfold, drop=drop,
+                  a2=a2, resid3=resid3, out_lo=out_lo, launch=plan[0])
         return
-    packed = w if isinstance(w, PackedW) else None
-    wrow = packed.row if packed is not None else w
-    M, N = (a.rows if is_kb(a) else a.shape[0]), wrow.shape[0]
-    Ka = wrow.shape[1]
-    if not K64_CFG14 and tile_cfg == 0 and auto_tile_cfg(M, N, Ka, a.element_size()) == 14:
-        tile_cfg = 8
-    if (TAIL_SPLIT and tile_cfg == 0 and out_group == 0 and resid_mod == 0 and a.is_cuda and drop is None and auto_tile_cfg(M, N, Ka, a.element_size()) == 8):
-        m_main = tail_split_rows(M, N, num_cus(a.device.index))
-        if (SHORT_K_WIDE_HALF_N and N >= SHORT_K_WIDE_HALF_N and Ka * a.element_size() <= SHORT_K_WIDE_HALF_BYTES and a.dtype == torch.bfloat16
-                and (SHORT_K_WIDE_HALF_STASH or aux_out is None)):
-            # short K loop, wide N (fc1 and its GELU' data gradient: K = 768, N = 3072): a quarter of a 256 x 256 launch is prologue + epilogue + hand-over that
-            # nothing overlaps (profiles/r04_d); on half-height tiles two workgroups share a CU and one's seam runs beside the other's K loop:
-            # 385 -> 338 us at M = 65 536, 266 -> 252 at 50 432 in isolation (bias + GELU store), level at N = 2304
-            tile_cfg, m_main = 14, M
-        if (m_main < M or HALF_HEIGHT_SHORT_K_ALWAYS) and HALF_HEIGHT_SHORT_K and CHAINS <= 1 and N <= 768 and Ka * a.element_size() <= 1536:      # (with other chains beside it a ragged round costs nothing: 40.99 -> 40.73 ms without this rule there)
-            # short K loops with a ragged last round (the image tower's output projection and its data gradient: 591 tiles on 256 CUs): the whole
-            # launch on half-height tiles, two workgroups per CU (tile cfg 14), instead of a main launch + a half-height tail launch — 1182 half
-            # tiles pack 2.31 rounds of 512, and one workgroup's epilogue runs beside its neighbour's K loop (round 3, isolated: 64 vs 62 + 21 us
-            # for the plain data gradient, 92 vs 102 us per 43 520 rows for the fp32-residual producer).  Longer K loops lose on it.
-            tile_cfg, m_main = 14, M
-        if m_main < M and CHAINS > 1 and not small_tail(M - m_main, N, num_cus(a.device.index)):
-            # several independent chains of launches share the chip (engine.contrastive_step: the image tower in two slices beside the text tower): a ragged last
-            # round is filled by the other chains' workgroups, and a tail launch BEHIND the main one only adds a launch (40.87 -> 40.70 ms).  Small tails still
-            # fork to the side stream: without that split the ViT-L/14 + LoRA step loses 2.4 ms (a handful of tiles as a whole extra round).
-            m_main = M
-        if m_main < M:
-            cut = lambda t, lo, hi: None if t is None else (t.row_range(lo, hi) if is_kb(t) else t[lo:hi])
-            slices = tail_k_slices(M - m_main, N, Ka, a.element_size(), num_cus(a.device.index))
 
-            def part(lo, hi, cfg, ws=None):
-                _gemm_one(cut(a, lo, hi), w, bias=bias, act=act, dact=dact, aux_in=cut(aux_in, lo, hi), aux_out=cut(aux_out, lo, hi), resid=cut(resid, lo, hi),
-                          resid_t=cut(resid_t, lo, hi), out_t=cut(out_t, lo, hi), out32=cut(out32, lo, hi), alpha=alpha, tile_cfg=cfg,
-                          resid_ln=None if resid_ln is None else (resid_ln[0][lo:hi],) + tuple(resid_ln[1:]), rowsum=cut(rowsum, lo, hi),
-                          lnfold=None if lnfold is None else (lnfold[0][lo:hi],) + tuple(lnfold[1:]), splitk_ws=ws if cfg >> 16 else None,
-                          resid3=None if resid3 is None else (cut(resid3[0], lo, hi), cut(resid3[1], lo, hi)), out_lo=cut(out_lo, lo, hi))
+    def run(launches):      # on whichever stream is current: the split-K scratch belongs to (device, stream)
+        ws = None
+        try:
+            for L in launches:
+                if L.scratch and ws is None:
+                    ws = splitk_workspace(L.scratch, a.device)
+                lo, hi = L.lo, L.hi
+                _gemm_one(_cut(a, lo, hi), w, bias=bias, act=act, dact=dact, aux_in=_cut(aux_in, lo, hi), aux_out=_cut(aux_out, lo, hi), resid=_cut(resid, lo, hi),
+                          resid_t=_cut(resid_t, lo, hi), out_t=_cut(out_t, lo, hi), out32=_cut(out32, lo, hi), alpha=alpha, resid_ln=_cut(resid_ln, lo, hi),
+                          rowsum=_cut(rowsum, lo, hi), lnfold=_cut(lnfold, lo, hi), splitk_ws=ws if L.scratch else None, a2=_cut(a2, lo, hi),
+                          resid3=_cut(resid3, lo, hi, 2), out_lo=_cut(out_lo, lo, hi), launch=L)
+        except Exception:
+            if ws is not None:      # phase 2 is what re-zeroes the shared scratch: an error between the two launches must not leave partial sums behind
+                drop_splitk_workspace(a.device)
+            raise
 
-            def tail():      # on whichever stream is current: the split-K scratch belongs to (device, stream)
-                ws = splitk_workspace(-(-(M - m_main) // 128) * -(-N // 256) * 128 * 256, a.device) if slices else None
-                try:
-                    for cfg in ((13 | slices << 16 | 1 << 22, 13 | slices << 16 | 2 << 22) if slices else (13,)):
-                        part(m_main, M, cfg, ws)
-                except Exception:
-                    if slices:      # phase 2 is what re-zeroes the shared scratch: an error between the two launches must not leave partial sums behind
-                        drop_splitk_workspace(a.device)
-                    raise
+    side = [L for L in plan if L.side]
+    if side:        # a small tail runs beside the main launch, not behind it
+        fork = _TailFork(a.device)
+        with fork:
+            run(side)
+        run([L for L in plan if not L.side])
+        fork.join()
+    else:
+        run(plan)
 
-            if small_tail(M - m_main, N, num_cus(a.device.index)):
-                fork = _TailFork(a.device)
-                with fork:
-                    tail()
-                part(0, m_main, big_tile_cfg(N, Ka, a.element_size()))
-                fork.join()
-            else:
-                part(0, m_main, big_tile_cfg(N, Ka, a.element_size()))
-                tail()
-            return
-    _gemm_one(a, w, bias=bias, act=act, dact=dact, aux_in=aux_in, aux_out=aux_out, resid=resid, resid_mod=resid_mod, resid_row_off=resid_row_off,
-              resid_t=resid_t, out_group=out_group, out_t=out_t, out32=out32, alpha=alpha, tile_cfg=tile_cfg, resid_ln=resid_ln,
-              rowsum=rowsum, lnfold=lnfold, drop=drop, resid3=resid3, out_lo=out_lo)
+
+def _plane(t, name, M, N, dtype, rows_checked=True):
+    """An epilogue operand that covers the [M, N] result as a row-major tensor ([>= M, >= N]) or a KBlocked one ([>= M, N]) of `dtype`:
+    (the tensor the kernel addresses, its row stride, the K-blocked plane stride in rows or 0)."""
+    if is_kb(t):
+        rows, cols, plane = _kb_dims(t, f"gemm {name}")
+        if rows < M or cols != N or t.t.dtype != dtype:
+            raise UiaError(f"gemm {name} (K-blocked {tuple(t.t.shape)} {t.t.dtype}) does not hold the [{M}, {N}] {dtype} plane")
+        return t.t, N, plane
+    if t.dtype != dtype or t.dim() != 2 or t.shape[1] < N or (rows_checked and t.shape[0] < M):
+        raise UiaError(f"gemm {name} is {tuple(t.shape)} {t.dtype}: it does not hold the [{M}, {N}] {dtype} plane")
+    return t, _rowmajor(t, name), 0
 
 
 def _gemm_one(a, w, *, bias=None, act=None, dact=None, aux_in=None, aux_out=None, resid=None, resid_mod=0, resid_row_off=0,
               resid_t=None, out_group=0, out_t=None, out32=None, alpha=1.0, tile_cfg=0, resid_ln=None, rowsum=None, lnfold=None, drop=None, splitk_ws=None, a2=None,
-              resid3=None, out_lo=None):
+              resid3=None, out_lo=None, launch=None):
+    """One uia_gemm launch: validate the operands, fill the descriptor, launch on `launch` (an entry of gemm()'s plan), or — called directly — on what
+    plan_gemm makes of `tile_cfg` for one launch of all rows."""
     d = GemmDesc()
     if splitk_ws is not None:
         d.splitk_ws = _p(splitk_ws)
@@ -605,56 +687,39 @@ def _gemm_one(a, w, *, bias=None, act=None, dact=None, aux_in=None, aux_out=None
                 raise UiaError("gemm drop: a_drop_out must have a's dtype, shape and strides")
             d.a_drop_out = _p(xo)
     packed = w if isinstance(w, PackedW) else None
-    if packed is not None:
-        w = packed.row
     if ext is not None:
-        # W exists K-blocked only and spans K = (columns of a) + K2; the launch runs on the ring tiles it was given (8 / 13)
+        # W exists K-blocked only and spans K = (columns of a) + K2
         d.lda, d.ldw, d.M, d.K, d.N = _rowmajor(a, "a"), ext.K, a.shape[0], ext.K, ext.N
-        d.A, d.W, d.w_kblocked = _p(a), _p(ext.kb), 1
-        base_cfg = (tile_cfg & 255) or (8 if d.M > 2048 else 13)
-        tile_cfg = (tile_cfg & ~255) | base_cfg
+        d.A = _p(a)
     else:
-        d.ldw = _rowmajor(w, "w")
+        wrow = packed.row if packed is not None else w
+        d.ldw = _rowmajor(wrow, "w")
         if is_kb(a):
             d.M, d.K, d.a_kb_rows = _kb_dims(a, "gemm a")
             d.lda = d.K
         else:
             d.lda = _rowmajor(a, "a")
             d.M, d.K = a.shape[0], a.shape[1]
-        if a.dtype != w.dtype or d.K != w.shape[1]:
-            raise UiaError(f"gemm operand mismatch: a {(d.M, d.K)} {a.dtype}, w {tuple(w.shape)} {w.dtype}")
-        d.A, d.W = _p(a.t if is_kb(a) else a), _p(w)
-        d.N = w.shape[0]
-        base_cfg = (tile_cfg & 255) or auto_tile_cfg(d.M, d.N, d.K, a.element_size())
-    # mirror of wide64_ok() in csrc/gemm.hip: the K = 64 read-modify-write stream (LoRA rank update / its data gradient) takes row-major W
-    if ((tile_cfg & 255) == 0 and base_cfg == 14 and a.dtype == torch.bfloat16 and d.K == 64 and d.N % 64 == 0 and d.N * 144 <= 160 * 1024 and not is_kb(a)
-            and not is_kb(out_t) and act is None and dact is None and aux_out is None and out_group == 0 and resid_mod == 0 and rowsum is None and lnfold is None
-            and resid_ln is None and (drop is None or drop[0] == "acc")
-            and ((out_t is not None and out32 is None and resid is None and (resid_t is not None or drop is not None))
-                 or (out32 is not None and out_t is None and resid_t is None and (resid is not None or drop is not None)))):
-        base_cfg = 23
-    if (tile_cfg & 255) == 0 and base_cfg == 8:
-        base_cfg = big_tile_cfg(d.N, d.K, a.element_size())
-        tile_cfg |= base_cfg
-    if (PERSIST_STORE_ONLY and base_cfg == 8 and resid is None and resid_t is None and out32 is None and rowsum is None and out_group == 0
-            and alpha == 1.0 and d.K * a.element_size() >= 1024):
-        base_cfg, tile_cfg = 12, (tile_cfg & ~255) | 12
-    if packed is not None and KBLOCK_W and base_cfg in RING_CFGS and a.is_cuda:
-        d.W, d.w_kblocked = _p(packed.kblocked()), 1
+        if a.dtype != wrow.dtype or d.K != wrow.shape[1]:
+            raise UiaError(f"gemm operand mismatch: a {(d.M, d.K)} {a.dtype}, w {tuple(wrow.shape)} {wrow.dtype}")
+        d.A = _p(a.t if is_kb(a) else a)
+        d.N = wrow.shape[0]
+    esz = a.element_size()
+    if launch is None:
+        launch = plan_gemm(d.M, d.N, d.K, esz, 0, tile_cfg, whole=True,
+                           **_plan_facts(a, w, act, dact, aux_out, out_group, resid_mod, drop, alpha, out_t, out32, resid, resid_t, rowsum, lnfold, resid_ln))[0]
+    tile_cfg, base_cfg = launch.tile_cfg, launch.base
+    d.W, d.w_kblocked = (_p(ext.kb if ext is not None else packed.kblocked()), 1) if launch.w_kblocked else (_p(wrow), 0)
     d.alpha = alpha
     d.act, d.dact = _ACT[act], _ACT[dact]
     if bias is not None:
         assert bias.dtype == torch.float32 and bias.numel() == d.N
         d.bias = _p(bias)
     for name, t, want in (("aux_in", aux_in, a.dtype), ("aux_out", aux_out, a.dtype), ("resid_t", resid_t, a.dtype),
-                          ("out_t", out_t, a.dtype), ("resid", resid, torch.float32), ("out32", out32, torch.float32)):
+                          ("resid", resid, torch.float32), ("out32", out32, torch.float32)):
         if t is not None and t.dtype != want:
             raise UiaError(f"gemm {name} must be {want}, got {t.dtype}")
-    if is_kb(out_t):
-        rows, cols, plane = _kb_dims(out_t, "gemm out_t")
-        if rows < d.M or cols != d.N or out_group:
-            raise UiaError(f"gemm out_t (K-blocked {tuple(out_t.t.shape)}) does not hold the [{d.M}, {d.N}] result")
-    for name, t in (("aux_in", aux_in), ("aux_out", aux_out), ("resid_t", resid_t), ("out_t", None if is_kb(out_t) else out_t), ("out32", out32)):
+    for name, t in (("aux_in", aux_in), ("aux_out", aux_out), ("resid_t", resid_t), ("out32", out32)):
         if t is not None and (t.dim() != 2 or t.shape[1] < d.N or (t.shape[0] < d.M and out_group == 0)):
             raise UiaError(f"gemm {name} is {tuple(t.shape)}: too small for the [{d.M}, {d.N}] result")
     if resid is not None and resid_mod == 0 and out_group == 0 and (resid.dim() != 2 or resid.shape[1] < d.N or resid.shape[0] < d.M):
@@ -690,53 +755,30 @@ def _gemm_one(a, w, *, bias=None, act=None, dact=None, aux_in=None, aux_out=None
     if resid_t is not None:
         d.residT, d.ldrT = _p(resid_t), _rowmajor(resid_t, "resid_t")
     if resid3 is not None:
-        hi3, lo3 = resid3
         if resid is not None or resid_t is not None:
             raise UiaError("gemm: resid3 replaces resid / resid_t")
-        if is_kb(hi3):
-            rows, cols, plane = _kb_dims(hi3, "gemm resid3 hi plane")
-            if rows < d.M or cols != d.N or hi3.t.dtype != torch.bfloat16:
-                raise UiaError(f"gemm resid3 hi plane (K-blocked {tuple(hi3.t.shape)}) does not hold the [{d.M}, {d.N}] bf16 residual")
-            d.residT, d.ldrT, d.residT_kb_rows = _p(hi3.t), d.N, plane
-        else:
-            if hi3.dtype != torch.bfloat16 or hi3.dim() != 2 or hi3.shape[0] < d.M or hi3.shape[1] < d.N:
-                raise UiaError(f"gemm resid3 hi plane {tuple(hi3.shape)} {hi3.dtype} does not hold the [{d.M}, {d.N}] bf16 residual")
-            d.residT, d.ldrT = _p(hi3), _rowmajor(hi3, "resid3 hi plane")
-        if is_kb(lo3):                                   # low bytes in 64-column blocks: KBlocked over an int8 [N/64, rows, 64] tensor
-            rows, cols, plane = _kb_dims(lo3, "gemm resid3 low bytes")
-            if rows < d.M or cols != d.N or lo3.t.dtype != torch.int8:
-                raise UiaError(f"gemm resid3 low bytes (blocked {tuple(lo3.t.shape)}) do not hold the [{d.M}, {d.N}] int8 plane")
-            d.resid_lo8, d.ld_resid_lo, d.resid_lo_kb_rows = _p(lo3.t), d.N, plane
-        else:
-            if lo3.dtype != torch.int8 or lo3.dim() != 2 or lo3.shape[0] < d.M or lo3.shape[1] < d.N:
-                raise UiaError(f"gemm resid3 low bytes {tuple(lo3.shape)} {lo3.dtype} do not hold the [{d.M}, {d.N}] int8 plane")
-            d.resid_lo8, d.ld_resid_lo = _p(lo3), _rowmajor(lo3, "resid3 low bytes")
+        t, d.ldrT, d.residT_kb_rows = _plane(resid3[0], "resid3 hi plane", d.M, d.N, torch.bfloat16)
+        d.residT = _p(t)
+        t, d.ld_resid_lo, d.resid_lo_kb_rows = _plane(resid3[1], "resid3 low bytes", d.M, d.N, torch.int8)      # K-blocked: in 64-column blocks, int8 [N/64, rows, 64]
+        d.resid_lo8 = _p(t)
     if out_lo is not None:
         if out_t is None:
             raise UiaError("gemm out_lo needs out_t (the hi plane)")
-        if is_kb(out_lo):
-            rows, cols, plane = _kb_dims(out_lo, "gemm out_lo")
-            if rows < d.M or cols != d.N or out_lo.t.dtype != torch.int8:
-                raise UiaError(f"gemm out_lo (blocked {tuple(out_lo.t.shape)}) does not hold the [{d.M}, {d.N}] int8 plane")
-            d.out_lo8, d.ld_out_lo, d.out_lo_kb_rows = _p(out_lo.t), d.N, plane
-        else:
-            if out_lo.dtype != torch.int8 or out_lo.dim() != 2 or out_lo.shape[0] < d.M or out_lo.shape[1] < d.N:
-                raise UiaError(f"gemm out_lo must be an int8 [{d.M}, {d.N}] plane")
-            d.out_lo8, d.ld_out_lo = _p(out_lo), _rowmajor(out_lo, "out_lo")
-    if is_kb(out_t):
-        d.outT, d.ldo, d.outT_kb_rows = _p(out_t.t), d.N, _kb_dims(out_t, "gemm out_t")[2]
-    elif out_t is not None:
-        d.outT, d.ldo = _p(out_t), _rowmajor(out_t, "out_t")
+        t, d.ld_out_lo, d.out_lo_kb_rows = _plane(out_lo, "out_lo", d.M, d.N, torch.int8)
+        d.out_lo8 = _p(t)
+    if out_t is not None:
+        if out_group and is_kb(out_t):
+            raise UiaError(f"gemm out_t (K-blocked {tuple(out_t.t.shape)}) does not hold the [{d.M}, {d.N}] result of a row-remapping launch")
+        t, d.ldo, d.outT_kb_rows = _plane(out_t, "out_t", d.M, d.N, a.dtype, not out_group)
+        d.outT = _p(t)
     if out32 is not None:
         d.out32, d.ldo32 = _p(out32), _rowmajor(out32, "out32")
-    if TILE_GROUP and d.N in TILE_GROUP and (tile_cfg >> 8) == 0 and base_cfg in RING_CFGS:
-        tile_cfg |= int(TILE_GROUP[d.N]) << 8
     if GEMM_PROFILE is not None:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
         check(lib().uia_gemm(_stream(), _code(a.dtype), C.byref(d), tile_cfg), "uia_gemm")
         e1.record()
-        esz = a.element_size()                  # algorithmic HBM bytes of this launch: every operand and result once
+        # algorithmic HBM bytes of this launch: every operand and result once
         nbytes = esz * (d.M * d.K + d.N * d.K) + d.M * d.N * (esz * sum(t is not None for t in (aux_in, aux_out, resid_t, out_t))
                                                              + 4 * sum(t is not None for t in (resid, out32)) + 3 * (resid3 is not None) + 1 * (out_lo is not None))
         mask = epi_mask_of(d)
