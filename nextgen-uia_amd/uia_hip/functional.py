@@ -20,8 +20,14 @@ import time
 
 import torch
 
-from . import ops
+from . import handoff, ops
 from ._lib import UiaError
+# The hand-offs that carry tensors BESIDE autograd between the Functions below (T copies of gradients, three-byte tokens, rows + row sums of a
+# folded LayerNorm) and the rules for handing them out live in uia_hip.handoff; these are its names as the engine, the models and the tests use
+# them.  MonaFn and VitBlockFn call them through THIS module's globals (tests replace publish_grad3 / publish_fwd3 here to count calls).
+from .handoff import (Resid3, _g3_partner_feeds, fwd3_of, grad3_decode, grad3_of, grad_resid3_enabled, hook_free, linear_chain,      # noqa: F401
+                      publish_fwd3, publish_grad3, publish_rows, publish_t_copy, set_grad_resid3, t_copy_of, take_rows, zero_sums)
+from .handoff import clear as clear_t_copies      # noqa: F401
 
 _STATE = {"dtype": torch.bfloat16, "seed": 0x5EED, "calls": 0, "fwd_resid3": os.environ.get("UIA_FWD_RESID3", "1") != "0"}
 
@@ -182,223 +188,6 @@ def set_dropout_seed(seed):
 def _next_seed():
     _STATE["calls"] += 1
     return (_STATE["seed"] * 0x9E3779B97F4A7C15 + _STATE["calls"] * 0xD1B54A32D192ED03) & 0xFFFFFFFFFFFFFFFF
-
-
-# ------------------------------------------------------------------------------------------------
-# T copies of fp32 gradient tensors travel beside autograd: the kernel that produces a residual
-# gradient also writes its T copy (operand of the consumer's first dgrad GEMM); the consumer looks
-# it up by storage address instead of re-reading 4 bytes/element to cast.
-_T_COPIES = {}
-
-
-def publish_t_copy(g32, g_t):
-    """The entry keeps a STRONG reference to the fp32 gradient: while it is registered its storage cannot be freed, so no
-    later tensor can appear at the same address and pick up a stale copy (a registry keyed by address alone did exactly that
-    when two backward passes ran without clear_t_copies() in between).  Entries are consumed by the first lookup; the
-    training loops clear what was never looked up once per step, and the registry is bounded besides."""
-    if g_t is not None and g_t.dtype != torch.float32:
-        if len(_T_COPIES) >= 256:
-            _T_COPIES.clear()
-        _T_COPIES[g32.data_ptr()] = (g32, g32._version, g_t)
-
-
-def t_copy_of(g32, dt, allow_kb=False):
-    """Return a T copy of the fp32 gradient `g32` (the one its producer published, if it is still that tensor's content).
-    allow_kb: the caller feeds the copy to a ring GEMM as its A operand and nothing else, so a K-blocked copy (3-D, ops.kb_empty) will do;
-    every other caller gets a row-major [.., D] tensor (a K-blocked publication is ignored and the copy is cast afresh)."""
-    if dt == torch.float32:
-        return g32
-    hit = _T_COPIES.pop(g32.data_ptr(), None)
-    if (hit is not None and hit[0].shape == g32.shape and hit[0].stride() == g32.stride() and hit[1] == g32._version
-            and hit[0].untyped_storage().data_ptr() == g32.untyped_storage().data_ptr() and hit[2].dtype == dt
-            and (allow_kb or not ops.is_kb(hit[2]))):
-        return hit[2]
-    out = torch.empty(g32.shape, device=g32.device, dtype=dt)
-    ops.cast(g32.contiguous(), out)
-    return out
-
-
-def clear_t_copies():
-    _T_COPIES.clear()
-    _ROWS.clear()
-    _SUMS_ARENA.clear()
-    _G3.clear()
-    _F3.clear()
-
-
-# ------------------------------------------------------------------------------------------------
-# THREE-BYTE residual gradients between the backward Functions of a frozen tower (round 4).  The fp32 gradient of the residual stream is
-# written by one row kernel (4 B + its 2-byte T copy) and read back by the next (4 B), three times per layer; as a three-byte tensor
-# (ops / include/uia_hip.h: bf16 hi plane — the T copy itself — plus one low byte) the same hand-off is 3 B written and 3 B read.  autograd
-# still wants a tensor of the gradient's shape: it gets a TOKEN — one NaN float expanded to that shape, no memory — and the planes travel
-# in this registry under the token's address.  Only MonaFn and VitBlockFn produce and consume tokens, a producer hands one out only when its
-# forward saw that the tensor it is the gradient of came straight (through views) from the other Function (so the token's only reader is
-# that Function's backward), and anything else that reads a token reads NaN: a topology this does not cover fails loudly, not quietly.
-# Opt-in per step (set_grad_resid3; engine.contrastive_step turns it on for hook-free towers).
-_G3 = {}
-_G3_POOL = {}
-_G3_VIEWS = ("PermuteBackward0", "ViewBackward0", "UnsafeViewBackward0", "TransposeBackward0", "AliasBackward0", "ReshapeAliasBackward0")
-_G3_PARTNERS = ("MonaFnBackward", "VitBlockFnBackward")
-
-
-def set_grad_resid3(flag):
-    _STATE["grad_resid3"] = bool(flag)
-
-
-def grad_resid3_enabled():
-    return bool(_STATE.get("grad_resid3", False))
-
-
-# Forward twin of the gradient tokens below: a residual-stream VALUE handed from MonaFn to the next block's VitBlockFn as (hi plane, low bytes, row sums).
-_F3 = {}
-_F3_POOL = {}
-
-
-def publish_fwd3(shape, device, hi, lo, sums):
-    key = (device.type, device.index if device.index is not None else (torch.cuda.current_device() if device.type == "cuda" else 0))
-    pool = _F3_POOL.get(key)
-    if pool is None:
-        pool = _F3_POOL[key] = [torch.full((256,), float("nan"), device=device, dtype=torch.float32), 0]
-    i = pool[1]
-    pool[1] = (i + 1) % 256
-    tok = pool[0][i:i + 1].view((1,) * len(shape)).expand(shape)
-    if len(_F3) >= 256:
-        _F3.clear()
-    _F3[tok.data_ptr()] = (hi, lo, sums, tok.numel())
-    return tok
-
-
-def fwd3_of(x):
-    """(hi, lo, sums) when x is a token of publish_fwd3 (consumed), else None.  Call BEFORE anything touches x's values (x.contiguous() would materialise NaNs)."""
-    if not _F3 or x.dim() == 0 or any(st != 0 for st, n in zip(x.stride(), x.shape) if n > 1):
-        return None
-    hit = _F3.pop(x.data_ptr(), None)
-    if hit is None or hit[3] != x.numel():
-        return None
-    return hit[0], hit[1], hit[2]
-
-
-class linear_chain:
-    """Scope of a tower's own block loop (forward_features / VisionTransformer.forward): inside it the residual stream is a plain chain block -> adapter -> block,
-    every block output has exactly ONE consumer, so a three-byte gradient token can stand in for its gradient.  Code that walks the blocks itself and taps
-    intermediate outputs (FPN heads, CLIPSeg's extract layers) never enters the scope and gets fp32 residual gradients (a token with a second
-    consumer would be ADDED to a real gradient by autograd)."""
-
-    def __enter__(self):
-        _STATE["chain_depth"] = _STATE.get("chain_depth", 0) + 1
-        return self
-
-    def __exit__(self, *exc):
-        _STATE["chain_depth"] -= 1
-        _STATE["fwd3_next_plain"] = False
-        return False
-
-    @staticmethod
-    def next_is_plain_block(flag):
-        """The tower's loop says, before it runs block i, whether block i + 1 exists and is a plain frozen block (VitBlockFn): only then may block i's adapter hand its
-        output over as a three-byte forward token (set_fwd_resid3)."""
-        _STATE["fwd3_next_plain"] = bool(flag)
-
-
-def hook_free(*modules):
-    """No forward / forward-pre / backward hook on any of the modules or their submodules, and no global module hook: nothing but the towers' own Functions
-    reads the tensors handed between them.  A three-byte forward token is a stride-0 NaN placeholder to everyone but its consumer (an activation
-    tap or Grad-CAM hook on a block would read NaNs; a hook that returns a new tensor would feed them into the next block)."""
-    import torch.nn.modules.module as _mm
-    if _mm._global_forward_hooks or _mm._global_forward_pre_hooks or _mm._global_backward_hooks or getattr(_mm, "_global_backward_pre_hooks", None) \
-            or getattr(_mm, "_global_forward_hooks_always_called", None):
-        return False
-    for mod in modules:
-        for m in mod.modules():
-            if m._forward_hooks or m._forward_pre_hooks or m._backward_hooks or getattr(m, "_backward_pre_hooks", None):
-                return False
-    return True
-
-
-def _g3_partner_feeds(x):
-    """True when x is the output of a MonaFn / VitBlockFn seen through view nodes only: the gradient this Function returns for x goes to that Function's backward."""
-    if not grad_resid3_enabled() or _STATE.get("chain_depth", 0) <= 0:
-        return False
-    fn = x.grad_fn
-    for _ in range(8):
-        if fn is None:
-            return False
-        name = type(fn).__name__
-        if name in _G3_PARTNERS:
-            return True
-        if name not in _G3_VIEWS or len(fn.next_functions) != 1:
-            return False
-        fn = fn.next_functions[0][0]
-    return False
-
-
-def publish_grad3(shape, device, hi, lo):
-    """Register the planes of a three-byte gradient and return the token autograd carries in its place."""
-    key = (device.type, device.index if device.index is not None else (torch.cuda.current_device() if device.type == "cuda" else 0))
-    pool = _G3_POOL.get(key)
-    if pool is None:
-        pool = _G3_POOL[key] = [torch.full((64,), float("nan"), device=device, dtype=torch.float32), 0]
-    i = pool[1]
-    pool[1] = (i + 1) % 64
-    tok = pool[0][i:i + 1].view((1,) * len(shape)).expand(shape)
-    if len(_G3) >= 64:
-        _G3.clear()
-    _G3[tok.data_ptr()] = (hi, lo, tok.numel())
-    return tok
-
-
-def grad3_of(g):
-    """(hi, lo) when g is a token of publish_grad3 (consumed), else None.  Call BEFORE anything touches g's values."""
-    if not _G3 or g.dim() == 0 or any(st != 0 for st, n in zip(g.stride(), g.shape) if n > 1):      # (a dimension of size 1 keeps whatever stride it had: a one-image slice)
-        return None
-    hit = _G3.pop(g.data_ptr(), None)
-    if hit is None or hit[2] != g.numel():
-        return None
-    return hit[0], hit[1]
-
-
-def grad3_decode(hi, lo):
-    """fp32 values of a three-byte gradient (slow path of a consumer that cannot take the planes: torch ops)."""
-    return ops.three_byte_to_float(hi, lo).contiguous()
-
-
-# Zeroed [M, 2] row-sum buffers for the producers of folded LayerNorms: slices of one arena that a single fill zeroes (a block needs two or
-# three of them per forward; 36 fills of 400 KB per step otherwise).  A slice is handed out once; the arena is dropped with the other
-# per-step registries (clear_t_copies) or when it runs out, and a new one is zeroed on the next request.  One arena per STREAM: the fill
-# that zeroes it and the atomics that land in its slices are ordered by that stream only (contrastive_step(overlap_text=True) runs the
-# text tower on a second stream; a shared arena would hand it slices with no event between the fill and their first use).
-_SUMS_ARENA = {}
-
-
-def _stream_key():
-    return ops.raw_stream()
-
-
-def zero_sums(M, device):
-    key = _stream_key()
-    a = _SUMS_ARENA.get(key)
-    if a is None or a[0].shape[1] != M or a[0].device != device or a[1] >= a[0].shape[0]:
-        a = [torch.zeros(48, M, 2, device=device, dtype=torch.int64), 0]
-        _SUMS_ARENA[key] = a
-    a[1] += 1
-    return a[0][a[1] - 1]
-
-
-# The forward twin of the registry above, one slot deep: the GEMM that produces a residual-stream tensor (Mona project2, a block's fc2)
-# can leave the T copy of its rows and their (Σ, Σ²) for the LayerNorm folded into the next block's first GEMM.
-_ROWS = {}          # one slot per stream (the producer and the consumer of a hand-off run on the same stream)
-
-
-def publish_rows(x32, x_t, sums):
-    _ROWS[_stream_key()] = (x32, x32._version, x_t, sums)
-
-
-def take_rows(x32, dt):
-    hit = _ROWS.pop(_stream_key(), None)
-    if (hit is not None and hit[0].data_ptr() == x32.data_ptr() and hit[0].numel() == x32.numel() and hit[1] == x32._version
-            and hit[0].untyped_storage().data_ptr() == x32.untyped_storage().data_ptr() and x32.is_contiguous() and hit[2].dtype == dt):
-        return hit[2], hit[3]
-    return None
 
 
 # ------------------------------------------------------------------------------------------------
@@ -671,58 +460,47 @@ class MonaFn(torch.autograd.Function):
         x = x.contiguous()
         M = B * N
         bott = P["project1.weight"].shape[0]
+        sp = {_SPATIAL_MAP[k]: v.detach().contiguous() for k, v in P.items() if k in _SPATIAL_MAP}
+        seed = _next_seed() if (p_drop > 0 and keep_mask is None) else 0
+        fold = ln_fold_enabled(dt, M)          # the next block's first LayerNorm is folded into its QKV GEMM: leave it the T rows and their sums
         if ops.mona_fused_ok(dt, D, h, w, bott):
             # the whole adapter in one launch (csrc/mona_fused.hip): u, t and d never travel through HBM between the stages
-            sp = {_SPATIAL_MAP[k]: v.detach().contiguous() for k, v in P.items() if k in _SPATIAL_MAP}
-            seed = _next_seed() if (p_drop > 0 and keep_mask is None) else 0
             train = any(ctx.needs_input_grad)
             u = _empty((M, D), dt, x) if train else None
             t = _empty((M, bott), dt, x) if train else None
             d = _empty((M, bott), dt, x) if train else None
             w1, w2 = WEIGHTS.get(P["project1.weight"], dt), WEIGHTS.get(P["project2.weight"], dt)
             y = torch.empty_like(x)
-            fold = ln_fold_enabled(dt, M)
-            y_t = _act(M, D, dt, x, 3 * D) if fold else None
-            sums = zero_sums(M, x.device) if fold else None
+            y_t, sums = (_act(M, D, dt, x, 3 * D), zero_sums(M, x.device)) if fold else (None, None)
             ops.mona_fused_fwd(variant, B, h, w, x, P["norm.weight"], P["norm.bias"], P["gamma"], P["gammax"], w1.row, P["project1.bias"], w2.row,
                                P["project2.bias"], sp, y, y_t=y_t, rowsum=sums, u_out=u, t_out=t, d_out=d, p_drop=p_drop, seed=seed, keep_mask=keep_mask)
             if fold:
                 publish_rows(y, y_t, sums)
-            if train:
-                ctx.save_for_backward(x, u, t, d, keep_mask if keep_mask is not None else x.new_empty(0), *params)
-            ctx.meta = (variant, hw, p_drop, seed, names, keep_mask is not None)
-            ctx.direct_params = tuple(params) if direct else None
-            ctx.g3_out = dt == torch.bfloat16 and _g3_partner_feeds(x)
-            return y
-        u = _empty((M, D), dt, x)
-        w1 = WEIGHTS.get(P["project1.weight"], dt)
-        t = _empty((M, bott), dt, x)
-        if ops.MONA_PRE_FWD_T and x.is_cuda and dt == torch.bfloat16 and D == 768 and bott == 64:
-            # project1 inside the row kernel: t from the u tile in LDS, u itself still written for the backward's weight gradient
-            ops.mona_pre_fwd(x, P["norm.weight"], P["norm.bias"], P["gamma"], P["gammax"], u, proj1=(w1.row if isinstance(w1, ops.PackedW) else w1, P["project1.bias"], t))
         else:
-            ops.mona_pre_fwd(x, P["norm.weight"], P["norm.bias"], P["gamma"], P["gammax"], u)
-            ops.gemm(u, w1, bias=P["project1.bias"], out_t=t)
-        sp = {_SPATIAL_MAP[k]: v.detach().contiguous() for k, v in P.items() if k in _SPATIAL_MAP}
-        d = _empty((M, bott), dt, x)
-        seed = _next_seed() if (p_drop > 0 and keep_mask is None) else 0
-        ops.mona_spatial_fwd(variant, B, h, w, t, sp, d, p_drop=p_drop, seed=seed, keep_mask=keep_mask)
-        w2 = WEIGHTS.get(P["project2.weight"], dt)
-        y = torch.empty_like(x)
-        if ln_fold_enabled(dt, M):             # the next block's first LayerNorm is folded into its QKV GEMM: leave it the T rows and their sums
-            y_t, sums = _act(M, D, dt, x, 3 * D), zero_sums(M, x.device)          # read by the next block's QKV GEMM only
-            if (dt == torch.bfloat16 and _STATE.get("fwd_resid3", True) and _STATE.get("fwd3_next_plain", False) and _STATE.get("chain_depth", 0) > 0 and M > 2048
-                    and x.is_cuda):
-                # the next block takes the sum as a THREE-BYTE tensor: its hi plane is the T copy, one low byte per element beside it; no fp32 rows are written
-                y_lo = torch.empty(M, D, device=x.device, dtype=torch.int8)
-                ops.gemm(d, w2, bias=P["project2.bias"], resid=x.view(M, D), out_t=y_t, out_lo=y_lo, rowsum=sums)
-                y = publish_fwd3(x.shape, x.device, y_t, y_lo, sums)
+            u = _empty((M, D), dt, x)
+            w1 = WEIGHTS.get(P["project1.weight"], dt)
+            t = _empty((M, bott), dt, x)
+            if ops.MONA_PRE_FWD_T and x.is_cuda and dt == torch.bfloat16 and D == 768 and bott == 64:
+                # project1 inside the row kernel: t from the u tile in LDS, u itself still written for the backward's weight gradient
+                ops.mona_pre_fwd(x, P["norm.weight"], P["norm.bias"], P["gamma"], P["gammax"], u, proj1=(w1.row if isinstance(w1, ops.PackedW) else w1, P["project1.bias"], t))
             else:
-                ops.gemm(d, w2, bias=P["project2.bias"], resid=x.view(M, D), out32=y.view(M, D), out_t=y_t, rowsum=sums)
+                ops.mona_pre_fwd(x, P["norm.weight"], P["norm.bias"], P["gamma"], P["gammax"], u)
+                ops.gemm(u, w1, bias=P["project1.bias"], out_t=t)
+            d = _empty((M, bott), dt, x)
+            ops.mona_spatial_fwd(variant, B, h, w, t, sp, d, p_drop=p_drop, seed=seed, keep_mask=keep_mask)
+            w2 = WEIGHTS.get(P["project2.weight"], dt)
+            y = torch.empty_like(x)
+            y_t, sums = (_act(M, D, dt, x, 3 * D), zero_sums(M, x.device)) if fold else (None, None)      # read by the next block's QKV GEMM only
+            # three: the next block takes the sum as a THREE-BYTE tensor: its hi plane is the T copy, one low byte per element beside it; no fp32 rows are written
+            three = fold and dt == torch.bfloat16 and _STATE.get("fwd_resid3", True) and handoff.fwd3_consumer_ahead() and M > 2048 and x.is_cuda
+            y_lo = torch.empty(M, D, device=x.device, dtype=torch.int8) if three else None
+            ops.gemm(d, w2, bias=P["project2.bias"], resid=x.view(M, D), out32=None if three else y.view(M, D), out_t=y_t, out_lo=y_lo, rowsum=sums)
+            if three:
+                y = publish_fwd3(x.shape, x.device, y_t, y_lo, sums)
+            elif fold:
                 publish_rows(y, y_t, sums)
-        else:
-            ops.gemm(d, w2, bias=P["project2.bias"], resid=x.view(M, D), out32=y.view(M, D))
-        ctx.save_for_backward(x, u, t, d, keep_mask if keep_mask is not None else x.new_empty(0), *params)
+        if u is not None:                                           # (the fused launch of a forward that needs no gradient kept nothing)
+            ctx.save_for_backward(x, u, t, d, keep_mask if keep_mask is not None else x.new_empty(0), *params)
         ctx.meta = (variant, hw, p_drop, seed, names, keep_mask is not None)
         ctx.direct_params = tuple(params) if direct else None      # the Parameter objects themselves: .grad is looked up at BACKWARD time
         ctx.g3_out = dt == torch.bfloat16 and _g3_partner_feeds(x)
@@ -738,12 +516,12 @@ class MonaFn(torch.autograd.Function):
         h, w = hw
         M, dt = B * N, u.dtype
         bott = t.shape[1]
-        g3 = grad3_of(dy)                                    # a three-byte gradient from the block behind this adapter: (T copy, low bytes)
+        g3 = grad3_of(dy)                                    # a three-byte gradient from the block behind this adapter: Resid3(T copy, low bytes)
         fuse_du = x.is_cuda and ops.mona_pre_bwd_du_ok(M, D, bott, dt)
-        if g3 is not None and ops.is_kb(g3[0]):
-            dy, g3 = grad3_decode(*g3).view(B, N, D), None   # a K-blocked hi plane is no operand of this backward's launches: back to fp32 (torch ops; not a path the towers take)
+        if g3 is not None and ops.is_kb(g3.hi):
+            dy, g3 = g3.decode().view(B, N, D), None         # a K-blocked hi plane is no operand of this backward's launches: back to fp32 (torch ops; not a path the towers take)
         if g3 is not None:
-            dy_t = g3[0].view(M, D)
+            dy_t = g3.hi.view(M, D)
         else:
             dy = dy.contiguous()
             dy_t = t_copy_of(dy, dt).view(M, D)
@@ -758,18 +536,7 @@ class MonaFn(torch.autograd.Function):
         w2t = WEIGHTS.get(P["project2.weight"], dt, transpose=True)          # [bott, D]
         dd = _empty((M, bott), dt, x)
         side = _wgrad_side_stream(x.device) if _STATE.get("wgrad_side_stream", False) else None
-        if side is not None:
-            # the two weight gradients of the adapter depend on nothing the data-gradient chain produces later: on a second stream they
-            # run beside its launches (whose lockstep phases and one-round kernels leave CUs and HBM idle)
-            cur = torch.cuda.current_stream()
-            side.wait_stream(cur)
-            with torch.cuda.stream(side):
-                ops.wgrad(dy_t, d, G["project2.weight"], G["project2.bias"])
-            dy_t.record_stream(side)
-            d.record_stream(side)
-        ops.gemm(dy_t, w2t, out_t=dd)
-        if side is None:
-            ops.wgrad(dy_t, d, G["project2.weight"], G["project2.bias"])
+        _wgrad_beside(side, lambda: ops.gemm(dy_t, w2t, out_t=dd), dy_t, d, G["project2.weight"], G["project2.bias"])
         # spatial
         sp = {_SPATIAL_MAP[k]: v.detach().contiguous() for k, v in P.items() if k in _SPATIAL_MAP}
         sg = {_SPATIAL_MAP[k]: G[k] for k in P if k in _SPATIAL_MAP}
@@ -778,16 +545,7 @@ class MonaFn(torch.autograd.Function):
         # project1: du = dt·W1 ; dW1 = dtᵀ·u ; db1 = Σ dt
         w1t = WEIGHTS.get(P["project1.weight"], dt, transpose=True)          # [D, bott]
         du = None if fuse_du else _empty((M, D), dt, x)                      # fuse_du: du = dt·W1 inside the row kernel below, no [M, D] round trip
-        if side is not None:
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                ops.wgrad(dtt, u, G["project1.weight"], G["project1.bias"])
-            dtt.record_stream(side)
-            u.record_stream(side)
-        if not fuse_du:
-            ops.gemm(dtt, w1t, out_t=du)
-        if side is None:
-            ops.wgrad(dtt, u, G["project1.weight"], G["project1.bias"])
+        _wgrad_beside(side, None if fuse_du else (lambda: ops.gemm(dtt, w1t, out_t=du)), dtt, u, G["project1.weight"], G["project1.bias"])
         need_dx = ctx.needs_input_grad[0]
         # the T copy of dx is the A operand of the preceding block's fc2 data-gradient GEMM (VitBlockFn.backward asks for it with
         # allow_kb): K-blocked when that launch runs on the ring kernels
@@ -801,7 +559,7 @@ class MonaFn(torch.autograd.Function):
             dx = publish_grad3(x.shape, x.device, dx_t, dlo)
         else:
             if need_dx and g3 is not None:                   # the block in front of this adapter does not take tokens: decode once, fp32 from here
-                dy = grad3_decode(*g3).view(B, N, D)
+                dy = g3.decode().view(B, N, D)
             dx = torch.empty_like(x) if need_dx else None
             ops.mona_pre_bwd(du, x, dy if need_dx else None, P["norm.weight"], P["norm.bias"], P["gamma"], P["gammax"], dx, dx_t,
                              G["gamma"], G["gammax"], G["norm.weight"], G["norm.bias"], dt_w1t=w1t_rows)
@@ -809,6 +567,23 @@ class MonaFn(torch.autograd.Function):
                 publish_t_copy(dx, dx_t)
         grads = tuple(None if direct else (G[k] if ctx.needs_input_grad[7 + i] else None) for i, k in enumerate(names))
         return (dx, None, None, None, None, None, None) + grads
+
+
+def _wgrad_beside(side, dgrad, a, b, dw, db):
+    """The weight gradient (dw, db) += (aᵀ·b, Σ a) of one adapter projection and that projection's data-gradient GEMM `dgrad` (a callable, or None when a row
+    kernel has taken it in).  side = None: the GEMM, then the weight gradient, on the current stream.  side = a second stream: the two weight gradients of the
+    adapter depend on nothing the data-gradient chain produces later, so the weight gradient is enqueued there FIRST and runs beside the GEMM and the launches
+    after it (whose lockstep phases and one-round kernels leave CUs and HBM idle)."""
+    if side is not None:
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            ops.wgrad(a, b, dw, db)
+        a.record_stream(side)
+        b.record_stream(side)
+    if dgrad is not None:
+        dgrad()
+    if side is None:
+        ops.wgrad(a, b, dw, db)
 
 
 _WGRAD_SIDE = {}
@@ -874,8 +649,8 @@ class VitBlockFn(torch.autograd.Function):
             raise UiaError(f"vit_block: {N} tokens exceed the {ATTN_SINGLE_PASS_MAX} of the attention backward; sequences this long run forward-only "
                            "(frozen tower under torch.no_grad()), unmasked" if ctx.needs_input_grad[0] else
                            f"vit_block: {N} tokens with a mask: the long attention forward takes no mask")
-        x3 = fwd3_of(x)                                   # the adapter in front handed its output over as a three-byte tensor (set_fwd_resid3): (hi = T rows, low bytes, row sums)
-        like = x3[1] if x3 is not None else x
+        x3 = fwd3_of(x)                                   # the adapter in front handed its output over as a three-byte tensor (set_fwd_resid3): Fwd3(hi = T rows, low bytes, row sums)
+        like = x3.lo if x3 is not None else x
         if x3 is None:
             x = x.contiguous()
             x2d = x.view(M, D)
@@ -883,14 +658,16 @@ class VitBlockFn(torch.autograd.Function):
         fold = ln_fold_enabled(dt, M)
         if x3 is not None:
             assert fold and dt == torch.bfloat16, "a three-byte forward token reached a block that cannot take it"
-            rows = (x3[0], x3[2])
+            rows = (x3.hi, x3.sums)
         else:
             rows = take_rows(x, dt) if fold else None    # (T copy of x, row sums) left by the GEMM that produced x
         qkv = _empty((M, 3 * D), dt, like)
         if rows is not None:                              # LN1 folded into the QKV GEMM
             wq, cq, bq = WEIGHTS.get_lnfold(spec.qkv[0], spec.qkv[1], spec.ln1[0], spec.ln1[1], dt)
-            xin_t = rows[0] if ops.is_kb(rows[0]) else rows[0].view(M, D)
-            ops.gemm(xin_t, wq, bias=bq, out_t=qkv, lnfold=(rows[1], cq, D, spec.eps))
+            xin_t, sums0 = rows
+            if not ops.is_kb(xin_t):
+                xin_t = xin_t.view(M, D)
+            ops.gemm(xin_t, wq, bias=bq, out_t=qkv, lnfold=(sums0, cq, D, spec.eps))
             h1 = _act(M, D, dt, like, spec.fc1[0].shape[0]) if x3 is not None else xin_t     # (fp32 x: the T copy's storage is free after this GEMM; three-byte x: it IS x's hi plane and lives on)
         else:
             h1 = _empty((M, D), dt, x)
@@ -920,11 +697,8 @@ class VitBlockFn(torch.autograd.Function):
         if fold:                                          # LN2 folded: proj leaves T rows + sums, fc1 normalises its accumulators
             sums1 = zero_sums(M, like.device)
             h1 = _as_act(h1, M, D, dt, F) if x3 is None else h1
-            resx = dict(resid3=(x3[0], x3[1])) if x3 is not None else dict(resid=x2d)
-            if r3:
-                ops.gemm(a, WEIGHTS.get(spec.proj[0], dt), bias=spec.proj[1], out_t=h1, out_lo=lo1, rowsum=sums1, **resx)
-            else:
-                ops.gemm(a, WEIGHTS.get(spec.proj[0], dt), bias=spec.proj[1], out32=x1, out_t=h1, rowsum=sums1, **resx)
+            resx = dict(resid3=x3.resid3) if x3 is not None else dict(resid=x2d)
+            ops.gemm(a, WEIGHTS.get(spec.proj[0], dt), bias=spec.proj[1], out32=x1, out_t=h1, out_lo=lo1, rowsum=sums1, **resx)    # (x1 or lo1: the other is None)
             w1, c1, b1 = WEIGHTS.get_lnfold(spec.fc1[0], spec.fc1[1], spec.ln2[0], spec.ln2[1], dt)
             ops.gemm(h1, w1, bias=b1, act=spec.act, aux_out=pre, out_t=f, lnfold=(sums1, c1, D, spec.eps))
         else:
@@ -933,7 +707,7 @@ class VitBlockFn(torch.autograd.Function):
             ops.layernorm_fwd(x1, spec.ln2[0], spec.ln2[1], spec.eps, y_t=h1)          # h1 buffer reused as h2
             ops.gemm(h1, WEIGHTS.get(spec.fc1[0], dt), bias=spec.fc1[1], act=spec.act, aux_out=pre, out_t=f)
         x2 = torch.empty(B, N, D, device=like.device, dtype=torch.float32)
-        res1 = dict(resid3=(h1, lo1)) if r3 else dict(resid=x1)
+        res1 = dict(resid3=Resid3(h1, lo1)) if r3 else dict(resid=x1)
         if fold and spec.publish_out:
             sums2 = zero_sums(M, like.device)
             h2 = _act(M, D, dt, like, 3 * D) if r3 else _as_act(h1, M, D, dt, 3 * D)      # (three-byte: h1 is x1's hi plane and stays alive)
@@ -942,44 +716,27 @@ class VitBlockFn(torch.autograd.Function):
         else:
             ops.gemm(f, WEIGHTS.get(spec.fc2[0], dt), bias=spec.fc2[1], out32=x2.view(M, D), **res1)
         if train:
-            ctx.a_kb = ops.is_kb(a)                       # save_for_backward takes tensors: the K-blocked wrapper is rebuilt in backward
-            ctx.r3, ctx.h1_kb = r3, bool(r3 and ops.is_kb(h1))
-            ctx.x3_kb = None if x3 is None else bool(ops.is_kb(x3[0]))       # three-byte block input: its two planes are what the LayerNorm backward recomputes from
+            # block input (three-byte: its two planes are what the LayerNorm backward recomputes from), qkv, a, lse, x1 (set_block_resid3: its planes), pre
+            saved, ctx.layout = handoff.save_layout(x3.resid3 if x3 is not None else x, qkv, a, lse, Resid3(h1, lo1) if r3 else x1, pre)
+            ctx.save_for_backward(*saved)
             ctx.xshape = (B, N, D)
-            xs = (x,) if x3 is None else ((x3[0].t if ctx.x3_kb else x3[0]), x3[1])
-            if r3:
-                ctx.save_for_backward(*xs, qkv, a.t if ctx.a_kb else a, lse, h1.t if ctx.h1_kb else h1, pre, lo1)
-            else:
-                ctx.save_for_backward(*xs, qkv, a.t if ctx.a_kb else a, lse, x1, pre)
             ctx.spec = spec
             ctx.g3_out = dt == torch.bfloat16 and _g3_partner_feeds(x)
         return x2
 
     @staticmethod
     def backward(ctx, dx2):
-        g3 = grad3_of(dx2)                                            # a three-byte gradient from the adapter behind this block: (T copy, possibly K-blocked; low bytes)
-        saved = list(ctx.saved_tensors)
-        if ctx.x3_kb is None:
-            x = saved.pop(0)
-            xin = None
-        else:                                                          # three-byte block input (set_fwd_resid3): (hi plane, low bytes)
-            xh, xl = saved.pop(0), saved.pop(0)
-            xin = (ops.KBlocked(xh) if ctx.x3_kb else xh, xl)
-            x = xl                                                     # device / allocation reference below
-        if ctx.r3:
-            qkv, a, lse, h1, pre, lo1 = saved
-            x1 = (ops.KBlocked(h1) if ctx.h1_kb else h1, lo1)         # three-byte x1: (hi plane, low bytes)
-        else:
-            qkv, a, lse, x1, pre = saved
-        if ctx.a_kb:
-            a = ops.KBlocked(a)
+        g3 = grad3_of(dx2)                                            # a three-byte gradient from the adapter behind this block: Resid3(T copy, possibly K-blocked; low bytes)
+        xin, qkv, a, lse, x1, pre = handoff.restore_layout(ctx.saved_tensors, ctx.layout)
+        x3_in, r3 = isinstance(xin, Resid3), isinstance(x1, Resid3)   # three-byte block input (set_fwd_resid3) / three-byte x1 (set_block_resid3)
+        x = xin.lo if x3_in else xin                                  # device / allocation reference below
         spec = ctx.spec
         B, N, D = ctx.xshape
         M, dt = B * N, qkv.dtype
         F = pre.shape[1]
         if g3 is not None:
-            dx2_t = g3[0] if ops.is_kb(g3[0]) else g3[0].view(M, D)
-            dres2 = (dx2_t, g3[1])
+            dx2_t = g3.hi if ops.is_kb(g3.hi) else g3.hi.view(M, D)
+            dres2 = Resid3(dx2_t, g3.lo)
         else:
             dx2 = dx2.contiguous()
             dx2_t = t_copy_of(dx2, dt, allow_kb=True)
@@ -993,11 +750,11 @@ class VitBlockFn(torch.autograd.Function):
         dh = _empty((M, D), dt, x)
         ops.gemm(dpre, WEIGHTS.get(spec.fc1[0], dt, transpose=True), out_t=dh)
         del dpre
-        if ctx.r3 or g3_mode:                                        # dx1 never leaves the block either: (T copy, low bytes), 3 bytes written instead of 4 + 2
+        if r3 or g3_mode:                                            # dx1 never leaves the block either: (T copy, low bytes), 3 bytes written instead of 4 + 2
             dx1_t = _empty((M, D), dt, x)
             dlo1 = torch.empty(M, D, device=x.device, dtype=torch.int8)
             ops.layernorm_bwd(dh, x1, spec.ln2[0], spec.eps, dres=dres2, dx_t=dx1_t, dx_lo=dlo1)
-            dx1 = (dx1_t, dlo1)
+            dx1 = Resid3(dx1_t, dlo1)
         else:
             dx1 = torch.empty_like(x1)
             dx1_t = _empty((M, D), dt, x) if dt != torch.float32 else dx1
@@ -1011,7 +768,7 @@ class VitBlockFn(torch.autograd.Function):
             ops.attn_bwd(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], a, da, lse, dqkv[:, :D], dqkv[:, D:2 * D], dqkv[:, 2 * D:], B, spec.heads, N, mask=spec.mask)
         ops.gemm(dqkv, WEIGHTS.get(spec.qkv[0], dt, transpose=True), out_t=da)       # dh1 into the same buffer
         dx_t = _empty((M, D), dt, x) if dt != torch.float32 else None
-        xrows = xin if xin is not None else x.view(M, D)
+        xrows = xin if x3_in else x.view(M, D)
         if getattr(ctx, "g3_out", False):
             dlo = torch.empty(M, D, device=x.device, dtype=torch.int8)
             ops.layernorm_bwd(da, xrows, spec.ln1[0], spec.eps, dres=dx1, dx_t=dx_t, dx_lo=dlo)
@@ -1041,7 +798,7 @@ class LnResidual:
 
     def gemm_kw(self):
         if self.lo is not None:
-            return dict(resid3=(self.hi, self.lo), resid_ln=(self.stats, self.w, self.b, self.dim, self.eps))
+            return dict(resid3=Resid3(self.hi, self.lo), resid_ln=(self.stats, self.w, self.b, self.dim, self.eps))
         if self.stats is None:
             return dict(resid=self.raw)
         if self.dim is None:

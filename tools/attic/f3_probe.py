@@ -1,3 +1,4 @@
+# attic: written against functional._F3 / _ROWS, which have moved to uia_hip.handoff (FWD3._live, _ROWS); not updated.
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "nextgen-uia_amd")]
