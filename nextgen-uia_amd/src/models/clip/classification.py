@@ -7,7 +7,6 @@ freeze_clip_backbone()); the loop is the BiomedCLIP entry point's (src/models/bi
 randomly initialised CLIP of the --model_config geometry (src/models/clip/finetune.py); --ckpt_path, when given, takes the place of --ckpt."""
 import argparse
 import logging
-import os
 import sys
 from pathlib import Path
 
@@ -20,7 +19,7 @@ from src.models.biomedclip import classification as _loop
 from src.models.biomedclip.zero_shot import load_adapter_by_name
 from src.models.clip.finetune import _geometry
 from src.third_party.openai_clip.clip_adapter import CLIPAdapter
-from src.third_party.openai_clip.model import CLIP, build_model
+from src.third_party.openai_clip.model import load_clip
 from src.utils.tools import default_device
 
 
@@ -59,17 +58,7 @@ def get_args(argv=None):
 
 def prepare_model(args):
     """reference :78-147."""
-    ckpt = args.ckpt_path or args.ckpt
-    if ckpt and os.path.exists(ckpt):
-        try:
-            sd = torch.jit.load(ckpt, map_location="cpu").state_dict()        # OpenAI's released checkpoints are TorchScript archives
-        except RuntimeError:
-            sd = torch.load(ckpt, map_location="cpu")
-        clip_model = build_model(sd)
-    else:
-        logging.info(f"checkpoint {ckpt} not found: randomly initialised CLIP {_geometry(args)}")
-        torch.manual_seed(args.seed)
-        clip_model = CLIP(*_geometry(args))
+    clip_model = load_clip(args.ckpt_path or args.ckpt, _geometry(args), args.seed)
     clip_model.float()
     if args.mona_weights:
         checkpoint = torch.load(args.mona_weights, map_location="cpu", weights_only=True)

@@ -10,7 +10,6 @@ Differences forced by the build image: `clip.load` (torchvision transforms, the 
 plain state dict when the file exists, otherwise the ViT-B/16 geometry is randomly initialised; captions are tokenised by the deterministic stand-in tokenizer (context 77,
 <start>/<end> ids of the CLIP vocabulary).  Added, non-breaking: --dtype, --synthetic / --data_pt, --model_config, data parallelism under torch.distributed.run."""
 import argparse
-import logging
 import os
 import random
 import sys
@@ -24,7 +23,7 @@ import torch
 from src.adapters import inject_mona_variant_to_clip
 from src.models.metaclip import finetune as _loop
 from src.third_party.open_clip.model import SyntheticClipTokenizer
-from src.third_party.openai_clip.model import CLIP, build_model
+from src.third_party.openai_clip.model import load_clip
 from src.utils.tools import default_device, parse_config, setup_logging
 
 
@@ -72,16 +71,7 @@ def make_tokenizer(args):
 
 def prepare_model(args):
     """reference :65-89: load CLIP, freeze everything, inject the Mona adapters, train only "mona" parameters, float32 masters."""
-    if args.ckpt and os.path.exists(args.ckpt):
-        try:
-            sd = torch.jit.load(args.ckpt, map_location="cpu").state_dict()        # OpenAI's released checkpoints are TorchScript archives (clip.py:128-136 of the reference)
-        except RuntimeError:
-            sd = torch.load(args.ckpt, map_location="cpu")
-        model = build_model(sd)
-    else:
-        logging.info(f"checkpoint {args.ckpt} not found: randomly initialised CLIP {_geometry(args)}")
-        torch.manual_seed(args.seed)
-        model = CLIP(*_geometry(args))
+    model = load_clip(args.ckpt, _geometry(args), args.seed)
     for p in model.parameters():
         p.requires_grad = False
     model, mona_count = inject_mona_variant_to_clip(model, variant=args.mona_variant, bottleneck_dim=args.mona_bottleneck, num_layers=args.mona_layers)

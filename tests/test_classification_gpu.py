@@ -329,6 +329,32 @@ def test_timm_adapter_keeps_a_batch_first_tower_batch_first():
         UF.set_compute_dtype(torch.bfloat16)
 
 
+def test_timm_adapter_on_a_sequence_first_tower_is_the_openai_adapter_bit_for_bit():
+    """TimmCLIPAdapter's third layout (visual.transformer, sequence-first blocks) and CLIPAdapter over one tower and one pyramid / seg-head state: the same
+    launches on the same operands, so the seg logits are equal bit for bit."""
+    from src.third_party.openai_clip.clip_adapter import CLIPAdapter
+    from src.third_party.openai_clip.model import CLIP
+    from src.third_party.timm.clip_adapter import TimmCLIPAdapter
+    from uia_hip import functional as UF
+    UF.set_compute_dtype(torch.float32)
+    try:
+        torch.manual_seed(5)
+        clip = CLIP(*CLIP_GEO)
+        kw = dict(extract_layers=[0, 1], reduce_dim=64, num_classes=2, img_size=32, patch_size=8, task="seg")
+        timm, openai = TimmCLIPAdapter(clip, **kw), CLIPAdapter(clip, **kw)
+        for part in ("reduces", "blocks", "seg_head"):
+            getattr(openai, part).load_state_dict(getattr(timm, part).state_dict())
+        timm, openai = timm.to(dev()).eval(), openai.to(dev()).eval()
+        timm.freeze_clip_backbone()                             # the shared tower: its embed() refuses a trainable ln_pre
+        images = torch.rand(3, 3, 32, 32, generator=torch.Generator().manual_seed(2)).to(dev())
+        with torch.no_grad():
+            y_timm, y_openai = timm(images), openai(images)
+        assert tuple(y_timm.shape) == (3, 2, 32, 32) and bool(torch.isfinite(y_timm).all()) and float(y_timm.abs().max()) > 0.0
+        assert torch.equal(y_timm, y_openai)
+    finally:
+        UF.set_compute_dtype(torch.bfloat16)
+
+
 # ------------------------------------------------------------------------------------------------ CLIs
 TOY = ["--synthetic", "--img_size", "32", "--patch_size", "8", "--reduce_dim", "64", "--batch_size", "8", "--synthetic_train", "48",
        "--synthetic_val", "16", "--synthetic_test", "16", "--device", "cuda:0", "--dtype", "fp32"]
