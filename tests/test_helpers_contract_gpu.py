@@ -5,17 +5,15 @@ element-wise against the float64 restatements of tests/helpers_reference.py, on 
 Every output is a view into a larger NaN-filled buffer: an element the kernel does not write fails its comparison, and a write
 outside the view (the guard regions, the padding columns of a strided view) fails the test.  Each test loops over its cases and
 collects every failure (bar, case, worst flat index, error/bound) before it fails once with the list."""
-import math
-
 import pytest
 import torch
 
 import helpers_reference as R
+from guarded_out import PAD, Out, dev, guards
 
 pytestmark = pytest.mark.gpu
 
 DT = (torch.bfloat16, torch.float32)
-PAD = 64                    # guard elements on each side of an output: keeps 128-byte (bf16) / 256-byte (fp32) alignment
 # threads of one sweep of each file's capped grid-stride launches: 4096 blocks (decoder.hip), 2048 (elementwise.hip), 16384 (heads.hip)
 SWEEP_DECODER, SWEEP_ELEMENTWISE, SWEEP_HEADS = 4096 * 256, 2048 * 256, 16384 * 256
 
@@ -32,10 +30,6 @@ def UiaError():
     return E
 
 
-def dev():
-    return torch.device("cuda:0")
-
-
 def rnd(*shape, seed=0, scale=1.0, shift=0.0):
     g = torch.Generator().manual_seed(seed)
     return torch.randn(*shape, generator=g) * scale + shift
@@ -43,34 +37,6 @@ def rnd(*shape, seed=0, scale=1.0, shift=0.0):
 
 def to_dev(t, dt=None):
     return t.to(dt if dt is not None else t.dtype).to(dev())
-
-
-class Out:
-    """A [rows, cols] (or `shape`) output view at offset PAD of a NaN-filled buffer, rows ld apart; `init` fills the view."""
-
-    def __init__(self, shape, dt, ld=None, init=None, offset=PAD):
-        shape = tuple(shape)
-        cols = shape[-1]
-        rows = math.prod(shape[:-1])
-        self.ld, self.cols, self.rows, self.offset = ld or cols, cols, rows, offset
-        self.buf = torch.full((offset + rows * self.ld + PAD,), float("nan"), dtype=dt, device=dev())
-        body = self.buf[offset:offset + rows * self.ld].view(rows, self.ld)
-        self.t = body[:, :cols] if self.ld != cols else body.view(shape)
-        if init is not None:
-            self.t.copy_(init.reshape(self.t.shape).to(dt))
-
-    def intact(self):
-        b = self.buf.cpu()
-        ok = bool(torch.isnan(b[:self.offset]).all()) and bool(torch.isnan(b[self.offset + self.rows * self.ld:]).all())
-        if self.ld != self.cols:
-            ok &= bool(torch.isnan(b[self.offset:self.offset + self.rows * self.ld].view(self.rows, self.ld)[:, self.cols:]).all())
-        return ok
-
-
-def guards(ck, bar, ctx, *outs):
-    for o in outs:
-        if not o.intact():
-            ck.fail(bar, ctx, "a write outside the output (guard region or padding columns)")
 
 
 def finish(ck):
