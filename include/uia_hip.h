@@ -540,17 +540,28 @@ int uia_adamw_clip_step_guarded(void* stream, size_t n, float* p, float* acc, fl
  *   UIA_CONVT_FWD  ConvTranspose2d k=2 s=2 of x1 [B,H,W,C1]: w [4·Cout][C1] (row (2·di+dj)·Cout + o), N = 4·Cout, N1 = N, bias [Cout];
  *                  y1 [B,2H,2W,Cout].
  *   UIA_CONVT_BWD  its data gradient: x1 = dy [B,2H,2W,C1 = Cout], w [N = Cin][4][Cout], y1 = dx [B,H,W,Cin], N1 = N.
- *   bias: fp32 or null.  MFMA path when C1, C2 % 32 == 0, N, N1 (and Cout) % 4 == 0 and operands 16-byte aligned; a direct path otherwise.
+ *   UIA_CONV1      Conv2d k=1 of x1 [B,H,W,C1] (the baseline UNet's conv1x1, src/third_party/unet.py:42): w [N][C1], N1 = N, y1 [B,H,W,N].
+ *                  The data gradient is the same call on dy with the transposed weight.
+ *   bias: fp32 or null.  MFMA path when C1, C2 % 8 == 0, N, N1 (and Cout) % 4 == 0 and operands 16-byte aligned; a direct path otherwise.
+ *   K = taps·(C1+C2) need not be a multiple of the 32-wide K step: the last step is zero-filled.  Shapes with C1, C2 % 32 == 0 run the
+ *   kernel they always ran (same bits).
  * uia_conv_wgrad: fp32 weight gradient over the B×H×W pixels in uia_conv_wgrad_splits(...) pixel ranges added in range order.
  *   UIA_CONV3      dw [N][9·(C1+C2)] from x1 / x2 and dy [B,H,W,N].
  *   UIA_CONVT_FWD  dw [4·N][C1] from x1 [B,H,W,C1] and dy [B,2H,2W,N] (N = Cout).
- *   ws: splits·rows·cols floats when splits > 1 (may be null otherwise). */
-enum { UIA_CONV3 = 0, UIA_CONVT_FWD = 1, UIA_CONVT_BWD = 2 };
-#define UIA_WGRAD_MAX_SPLITS 64            /* MFMA path (channels % 32, N % 8) */
+ *   UIA_CONV1      dw [N][C1] from x1 [B,H,W,C1] and dy [B,H,W,N].
+ *   ws: splits·rows·cols floats when splits > 1 (may be null otherwise).  MFMA path when C1, C2 % 8 == 0 and N % 8 == 0.
+ * uia_conv_igemm_form / uia_conv_wgrad_form: 1 when the matrix-core kernel is taken for 16-byte-aligned operands, 0 for the direct
+ *   kernel (pure functions of the shape, callable without a GPU; the launchers decide by them).  They tell which of the baseline UNet's
+ *   layers (src/third_party/unet.py:5-111, init_channels = 16) leave the direct kernel: all but the 3-channel input and num_classes output. */
+enum { UIA_CONV3 = 0, UIA_CONVT_FWD = 1, UIA_CONVT_BWD = 2, UIA_CONV1 = 3 };
+#define UIA_WGRAD_MAX_SPLITS 64            /* MFMA path, C1 and C2 multiples of 32 (N % 8) */
+#define UIA_WGRAD_MAX_NARROW_SPLITS 512    /* MFMA path, C1 or C2 not a multiple of 32 (few tiles, the most pixels) */
 #define UIA_WGRAD_MAX_DIRECT_SPLITS 1024    /* direct path (few channels) */
 int uia_conv_igemm(void* stream, int dtype, int mode, int B, int H, int W, int C1, int C2, const void* x1, const void* x2, int N, int N1,
                    const void* w, const float* bias, void* y1, void* y2);
 int uia_conv_wgrad_splits(int mode, int B, int H, int W, int C1, int C2, int N);
+int uia_conv_igemm_form(int mode, int C1, int C2, int N, int N1);
+int uia_conv_wgrad_form(int mode, int C1, int C2, int N);
 int uia_conv_wgrad(void* stream, int dtype, int mode, int B, int H, int W, int C1, int C2, const void* x1, const void* x2, int N, const void* dy,
                    float* ws, float* dw);
 /* BatchNorm2d (+ ReLU when relu != 0) on y [M = B·H·W, C] (dtype elements), fp32 parameters and buffers.
@@ -566,6 +577,24 @@ int uia_bn_fwd(void* stream, int dtype, int training, int64_t M, int C, const vo
 int uia_bn_relu_bwd(void* stream, int dtype, int64_t M, int C, const void* y, const void* dout, const float* scale, const float* shift,
                     const float* mean, const float* invstd, const float* gamma, float* ws, float* dgamma, float* dbeta, void* dy);
 int uia_colsum_ordered(void* stream, int dtype, int64_t M, int C, const void* y, float* ws, float* out);
+/* BatchNorm2d + LeakyReLU(slope) + Dropout(drop_p) of the baseline UNet's ConvBlock (src/third_party/unet.py:10-18), on the arguments of
+ * uia_bn_fwd / uia_bn_relu_bwd:  out = leaky(z)·keep/(1−drop_p), z = y·scale + shift, leaky(z) = z > 0 ? z : slope·z.
+ *   Statistics, running buffers and scale / shift are exactly uia_bn_fwd's.  keep: keep_mask (uint8 [M, C]) when non-null, else, when
+ *   drop_p > 0, the counter hash of (seed, flat element index / 8), the generator of uia_dropout (needs M·C % 8 == 0).  No dropout when
+ *   drop_p == 0 or training == 0.  uia_bn_act_bwd: dz = dout·keep/(1−drop_p)·(z > 0 ? 1 : slope) (z == 0 takes the slope), then as
+ *   uia_bn_relu_bwd.  slope = 0, drop_p = 0 gives uia_bn_fwd(relu = 1) bit for bit. */
+int uia_bn_act_fwd(void* stream, int dtype, int training, int64_t M, int C, const void* y, const float* gamma, const float* beta, float* running_mean,
+                   float* running_var, int64_t* num_batches_tracked, float momentum, float eps, float* ws, float* mean, float* invstd, float* scale,
+                   float* shift, float slope, void* out, float drop_p, uint64_t seed, const uint8_t* keep_mask);
+int uia_bn_act_bwd(void* stream, int dtype, int64_t M, int C, const void* y, const void* dout, const float* scale, const float* shift,
+                   const float* mean, const float* invstd, const float* gamma, float* ws, float* dgamma, float* dbeta, void* dy, float slope,
+                   float drop_p, uint64_t seed, const uint8_t* keep_mask);
+/* nn.MaxPool2d(2) of the baseline UNet's DownBlock (src/third_party/unet.py:29) on NHWC x [B,H,W,C] -> y [B,H/2,W/2,C] (floor: a trailing
+ *   odd row / column is ignored).  Backward: the argmax is recomputed from x (ties to the first maximum in the order (0,0), (0,1), (1,0),
+ *   (1,1), as PyTorch) and every element of dx [B,H,W,C] is written (zeros off the argmax and in the trailing row / column): no atomics,
+ *   no memset.  H < 2 or W < 2 is refused. */
+int uia_maxpool2_fwd(void* stream, int dtype, int B, int H, int W, int C, const void* x, void* y);
+int uia_maxpool2_bwd(void* stream, int dtype, int B, int H, int W, int C, const void* x, const void* dy, void* dx);
 /* uia_upsample_ac: bilinear, align_corners=True, integer factor f on NHWC: forward in [B,H,W,C] -> out [B,fH,fW,C]; backward (gather,
  *   no atomics) in = dout [B,fH,fW,C] -> out = dx [B,H,W,C].
  * uia_resize_aa: F.interpolate(bicubic, antialias=True, align_corners=False) from NHWC x [B,Hi,Wi,C] (dtype) to NCHW fp32 out

@@ -254,6 +254,24 @@ int uia_bn_relu_bwd(void* stream, int dtype, int64_t M, int C, const void* y, co
 int uia_colsum_ordered(void* stream, int dtype, int64_t M, int C, const void* y, float* ws, float* out) {
     return uia_colsum_ordered_launch((hipStream_t)stream, dtype, (long)M, C, y, ws, out);
 }
+int uia_bn_act_fwd(void* stream, int dtype, int training, int64_t M, int C, const void* y, const float* gamma, const float* beta, float* running_mean,
+                   float* running_var, int64_t* num_batches_tracked, float momentum, float eps, float* ws, float* mean, float* invstd, float* scale,
+                   float* shift, float slope, void* out, float drop_p, uint64_t seed, const uint8_t* keep_mask) {
+    return uia_bn_act_fwd_launch((hipStream_t)stream, dtype, training, (long)M, C, y, gamma, beta, running_mean, running_var, num_batches_tracked, momentum,
+                                 eps, ws, mean, invstd, scale, shift, slope, out, drop_p, seed, keep_mask);
+}
+int uia_bn_act_bwd(void* stream, int dtype, int64_t M, int C, const void* y, const void* dout, const float* scale, const float* shift,
+                   const float* mean, const float* invstd, const float* gamma, float* ws, float* dgamma, float* dbeta, void* dy, float slope,
+                   float drop_p, uint64_t seed, const uint8_t* keep_mask) {
+    return uia_bn_act_bwd_launch((hipStream_t)stream, dtype, (long)M, C, y, dout, scale, shift, mean, invstd, gamma, ws, dgamma, dbeta, dy, slope, drop_p,
+                                 seed, keep_mask);
+}
+int uia_maxpool2_fwd(void* stream, int dtype, int B, int H, int W, int C, const void* x, void* y) {
+    return uia_maxpool2_launch((hipStream_t)stream, dtype, 0, B, H, W, C, x, nullptr, y);
+}
+int uia_maxpool2_bwd(void* stream, int dtype, int B, int H, int W, int C, const void* x, const void* dy, void* dx) {
+    return uia_maxpool2_launch((hipStream_t)stream, dtype, 1, B, H, W, C, x, dy, dx);
+}
 int uia_upsample_ac(void* stream, int dtype, int backward, int B, int H, int W, int C, int f, const void* in, void* out) {
     return uia_upsample_ac_launch((hipStream_t)stream, dtype, backward, B, H, W, C, f, in, out);
 }

@@ -98,6 +98,15 @@ int uia_bn_fwd_launch(hipStream_t stream, int dtype, int training, long M, int C
 int uia_bn_relu_bwd_launch(hipStream_t stream, int dtype, long M, int C, const void* y, const void* dout, const float* scale, const float* shift,
                            const float* mean, const float* invstd, const float* gamma, float* ws, float* dgamma, float* dbeta, void* dy);
 int uia_colsum_ordered_launch(hipStream_t stream, int dtype, long M, int C, const void* y, float* ws, float* out);
+int uia_conv_igemm_form(int mode, int C1, int C2, int N, int N1);
+int uia_conv_wgrad_form(int mode, int C1, int C2, int N);
+int uia_bn_act_fwd_launch(hipStream_t stream, int dtype, int training, long M, int C, const void* y, const float* gamma, const float* beta,
+                          float* run_mean, float* run_var, int64_t* nbt, float momentum, float eps, float* ws, float* mean, float* invstd,
+                          float* scale, float* shift, float slope, void* out, float drop_p, uint64_t seed, const uint8_t* keep_mask);
+int uia_bn_act_bwd_launch(hipStream_t stream, int dtype, long M, int C, const void* y, const void* dout, const float* scale, const float* shift,
+                          const float* mean, const float* invstd, const float* gamma, float* ws, float* dgamma, float* dbeta, void* dy,
+                          float slope, float drop_p, uint64_t seed, const uint8_t* keep_mask);
+int uia_maxpool2_launch(hipStream_t stream, int dtype, int backward, int B, int H, int W, int C, const void* x, const void* dy, void* out);
 int uia_upsample_ac_launch(hipStream_t stream, int dtype, int backward, int B, int H, int W, int C, int f, const void* in, void* out);
 int uia_resize_aa_launch(hipStream_t stream, int dtype, int backward, int B, int C, int Hi, int Wi, int Ho, int Wo, const void* x, float* tmp, float* out,
                          const float* dout, void* dx);

@@ -1,5 +1,6 @@
-// unet_bn.hip — BatchNorm2d + ReLU of the DINOv2 UNet decoder on NHWC rows [M = B·H·W, C], and plain column sums (the convs' bias
-// gradients).
+// unet_bn.hip — BatchNorm2d + ReLU of the DINOv2 UNet decoder on NHWC rows [M = B·H·W, C], plain column sums (the convs' bias
+// gradients), and BatchNorm2d + LeakyReLU + Dropout of the baseline UNet's ConvBlock (the reference's src/third_party/unet.py:10-18) on the
+// same statistics kernels.
 //
 // Replaces: nn.BatchNorm2d(eps 1e-5, momentum 0.1) + nn.ReLU of UNetDecoderUpBlock (the reference's src/third_party/dino/dinov2.py:130-152)
 //           in training and eval mode, forward and backward.
@@ -151,6 +152,161 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(long M, int C, const 
     dy[i] = from_f32<T>(gamma[c] * is * (dz - dbeta[c] * inv - xh * dgamma[c] * inv));
 }
 
+// ---------------------------------------------------------------- BatchNorm + LeakyReLU + Dropout (the baseline UNet's ConvBlock)
+// keep·1/(1−p) of element i: the explicit mask, else the draw of uia_dropout (one dropout_keep8 per eight consecutive elements)
+struct Drop {
+    const uint8_t* mask;
+    uint64_t seed;
+    uint32_t thresh16;
+    float inv_keep;
+    int on;
+};
+__device__ __forceinline__ float drop_factor(const Drop& d, long i) {
+    if (!d.on) return 1.f;
+    const bool keep = d.mask ? d.mask[i] != 0 : ((dropout_keep8(d.seed, (uint32_t)(i >> 3), d.thresh16) >> (i & 7)) & 1u) != 0;
+    return keep ? d.inv_keep : 0.f;
+}
+// the factors of the eight consecutive elements starting at i0 (a multiple of 8): one draw of the generator, or eight mask bytes in one load
+__device__ __forceinline__ void drop_factors8(const Drop& d, long i0, float (&k)[8]) {
+    if (d.mask) {
+        const uint64_t m = *(const uint64_t*)(d.mask + i0);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) k[e] = (m >> (8 * e)) & 0xFFu ? d.inv_keep : 0.f;
+    } else {
+        const uint32_t m = dropout_keep8(d.seed, (uint32_t)(i0 >> 3), d.thresh16);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) k[e] = (m >> e) & 1u ? d.inv_keep : 0.f;
+    }
+}
+// the eight-element kernels serve both kinds of mask under the same conditions, so a generated mask and the same mask passed explicitly give
+// the same bits: dropout on, a multiple of 8 elements, 16-byte-aligned tensors (8-byte-aligned mask)
+bool drop8_ok(const Drop& d, long n, const void* a, const void* b, const void* c) {
+    return d.on && n % 8 == 0 && ((((uintptr_t)a | (uintptr_t)b | (uintptr_t)c) & 15) == 0) && (((uintptr_t)d.mask & 7) == 0);
+}
+// dz = dout·keep/(1−p)·leaky'(z); z == 0 takes the slope, as PyTorch's leaky_relu backward
+__device__ __forceinline__ float act_dz(float z, float dout, float slope, const Drop& d, long i) {
+    float g = dout;
+    if (d.on) g *= drop_factor(d, i);
+    return z > 0.f ? g : g * slope;
+}
+
+// one element of the forward before dropout, and of the backward after dz: shared by the one- and the eight-element kernels
+__device__ __forceinline__ float act_fwd_elem(float y, float sc, float sh, float slope) {
+    const float v = fmaf(y, sc, sh);
+    return v > 0.f ? v : (slope == 0.f ? 0.f : slope * v);
+}
+__device__ __forceinline__ float bn_bwd_elem(float v, float dz, float mu, float is, float gamma, float dbeta, float dgamma, float inv) {
+    const float xh = (v - mu) * is;
+    return gamma * is * (dz - dbeta * inv - xh * dgamma * inv);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void bn_act_apply_kernel(long n, int C, const T* __restrict__ y, const float* __restrict__ scale,
+                                                           const float* __restrict__ shift, float slope, Drop d, T* __restrict__ out) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int c = (int)(i % C);
+    float v = act_fwd_elem(to_f32(y[i]), scale[c], shift[c], slope);
+    if (d.on) v *= drop_factor(d, i);
+    out[i] = from_f32<T>(v);
+}
+
+// the same with dropout on: eight consecutive elements per thread, so one draw of the generator serves the eight it covers
+template <typename T>
+__global__ __launch_bounds__(256) void bn_act_apply8_kernel(long n, int C, const T* __restrict__ y, const float* __restrict__ scale,
+                                                            const float* __restrict__ shift, float slope, Drop d, T* __restrict__ out) {
+    const long i0 = ((long)blockIdx.x * 256 + threadIdx.x) * 8;
+    if (i0 >= n) return;
+    float v[8], k[8];
+    load8(y + i0, v);
+    drop_factors8(d, i0, k);
+    int c = (int)(i0 % C);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        v[e] = act_fwd_elem(v[e], scale[c], shift[c], slope) * k[e];
+        if (++c == C) c = 0;
+    }
+    store8(out + i0, v);
+}
+
+// reduce_kernel<RED_BWD> with the activation's dz
+template <typename T>
+__global__ __launch_bounds__(256) void reduce_act_bwd_kernel(long M, int C, const T* __restrict__ y, const T* __restrict__ dout,
+                                                             const float* __restrict__ scale, const float* __restrict__ shift,
+                                                             const float* __restrict__ mean, const float* __restrict__ invstd, float slope, Drop d,
+                                                             float* __restrict__ ws) {
+    __shared__ float red[2][256];
+    const int S = gridDim.x, s = blockIdx.x, tid = threadIdx.x;
+    const long per = (M + S - 1) / S;
+    const long rb = (long)s * per, re = rb + per < M ? rb + per : M;
+    const int Cb = C < 256 ? C : 256, RP = 256 / Cb;
+    for (int cbase = 0; cbase < C; cbase += Cb) {
+        const int c = cbase + tid % Cb, rl = tid / Cb;
+        const bool act = rl < RP && c < C;
+        float a = 0.f, q = 0.f;
+        if (act && rb < re) {
+            const float sc = scale[c], sh = shift[c], mu = mean[c], is = invstd[c];
+            for (long r = rb + rl; r < re; r += RP) {
+                const float v = to_f32(y[r * C + c]);
+                const float dz = act_dz(fmaf(v, sc, sh), to_f32(dout[r * C + c]), slope, d, r * C + c);
+                a += dz;
+                q = fmaf(dz, (v - mu) * is, q);
+            }
+        }
+        red[0][tid] = a;
+        red[1][tid] = q;
+        __syncthreads();
+        if (rl == 0 && c < C) {
+            for (int k = 1; k < RP; ++k) {
+                a += red[0][tid + k * Cb];
+                q += red[1][tid + k * Cb];
+            }
+            float* o = ws + ((size_t)s * C + c) * 3;
+            o[0] = a;
+            o[1] = q;
+            o[2] = 0.f;
+        }
+        __syncthreads();
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void bn_act_bwd_apply_kernel(long M, int C, const T* __restrict__ y, const T* __restrict__ dout, const float* __restrict__ scale,
+                                                               const float* __restrict__ shift, const float* __restrict__ mean, const float* __restrict__ invstd,
+                                                               const float* __restrict__ gamma, const float* __restrict__ dbeta, const float* __restrict__ dgamma,
+                                                               float slope, Drop d, T* __restrict__ dy) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= M * C) return;
+    const int c = (int)(i % C);
+    const float v = to_f32(y[i]);
+    const float dz = act_dz(fmaf(v, scale[c], shift[c]), to_f32(dout[i]), slope, d, i);
+    dy[i] = from_f32<T>(bn_bwd_elem(v, dz, mean[c], invstd[c], gamma[c], dbeta[c], dgamma[c], 1.0f / (float)M));
+}
+
+// the same with dropout on, eight consecutive elements per thread (see bn_act_apply8_kernel)
+template <typename T>
+__global__ __launch_bounds__(256) void bn_act_bwd_apply8_kernel(long M, int C, const T* __restrict__ y, const T* __restrict__ dout, const float* __restrict__ scale,
+                                                                const float* __restrict__ shift, const float* __restrict__ mean, const float* __restrict__ invstd,
+                                                                const float* __restrict__ gamma, const float* __restrict__ dbeta, const float* __restrict__ dgamma,
+                                                                float slope, Drop d, T* __restrict__ dy) {
+    const long i0 = ((long)blockIdx.x * 256 + threadIdx.x) * 8;
+    if (i0 >= M * C) return;
+    float v[8], g[8], k[8];
+    load8(y + i0, v);
+    load8(dout + i0, g);
+    drop_factors8(d, i0, k);
+    const float inv = 1.0f / (float)M;
+    int c = (int)(i0 % C);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const float gk = g[e] * k[e];
+        const float dz = fmaf(v[e], scale[c], shift[c]) > 0.f ? gk : gk * slope;
+        v[e] = bn_bwd_elem(v[e], dz, mean[c], invstd[c], gamma[c], dbeta[c], dgamma[c], inv);
+        if (++c == C) c = 0;
+    }
+    store8(dy + i0, v);
+}
+
 int slices_for(long M) { long s = (M + 255) / 256; return (int)(s < UIA_BN_SLICES ? s : UIA_BN_SLICES); }
 
 }  // namespace
@@ -223,6 +379,97 @@ int uia_bn_relu_bwd_launch(hipStream_t stream, int dtype, long M, int C, const v
     else
         hipLaunchKernelGGL(bn_bwd_apply_kernel<float>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, M, C, (const float*)y, (const float*)dout, scale, shift,
                            mean, invstd, gamma, dbeta, dgamma, (float*)dy);
+    UIA_CHECK_LAUNCH();
+    return 0;
+}
+
+// the dropout of one call: off in eval mode and at drop_p == 0
+static int drop_of(const char* fn, int training, long n, float drop_p, uint64_t seed, const uint8_t* keep_mask, Drop* d) {
+    UIA_CHECK_ARG(drop_p >= 0.f && drop_p < 1.f, "%s: drop_p=%f outside [0, 1)", fn, drop_p);
+    *d = Drop{nullptr, seed, 0u, 1.f, 0};
+    if (!training || drop_p == 0.f) return 0;
+    UIA_CHECK_ARG(keep_mask || (n % 8 == 0 && n / 8 <= 0xFFFFFFFFl), "%s: the generated mask needs M*C=%ld a multiple of 8 within the generator's 2^35 elements", fn, n);
+    *d = Drop{keep_mask, seed, dropout_thresh16(drop_p), 1.0f / (1.0f - drop_p), 1};
+    return 0;
+}
+
+int uia_bn_act_fwd_launch(hipStream_t stream, int dtype, int training, long M, int C, const void* y, const float* gamma, const float* beta,
+                          float* run_mean, float* run_var, int64_t* nbt, float momentum, float eps, float* ws, float* mean, float* invstd,
+                          float* scale, float* shift, float slope, void* out, float drop_p, uint64_t seed, const uint8_t* keep_mask) {
+    BN_ARGS_OK("uia_bn_act_fwd");
+    UIA_CHECK_ARG(y && gamma && beta && scale && shift && out, "uia_bn_act_fwd: null tensor");
+    UIA_CHECK_ARG(eps > 0.f && momentum >= 0.f && momentum <= 1.f, "uia_bn_act_fwd: eps must be > 0 and momentum in [0, 1]");
+    UIA_CHECK_ARG(slope >= 0.f && slope <= 1.f, "uia_bn_act_fwd: slope=%f outside [0, 1]", slope);
+    Drop d;
+    if (drop_of("uia_bn_act_fwd", training, M * C, drop_p, seed, keep_mask, &d)) return -1;
+    if (training) {
+        UIA_CHECK_ARG(ws && mean && invstd, "uia_bn_act_fwd: training needs ws, mean and invstd");
+        UIA_CHECK_ARG((run_mean == nullptr) == (run_var == nullptr), "uia_bn_act_fwd: running mean and variance come together");
+        const int S = slices_for(M);
+        if (dtype == UIA_BF16)
+            hipLaunchKernelGGL((reduce_kernel<bf16_t, RED_STATS>), dim3(S), dim3(256), 0, stream, M, C, (const bf16_t*)y, nullptr, nullptr, nullptr, nullptr, nullptr, ws);
+        else
+            hipLaunchKernelGGL((reduce_kernel<float, RED_STATS>), dim3(S), dim3(256), 0, stream, M, C, (const float*)y, nullptr, nullptr, nullptr, nullptr, nullptr, ws);
+        UIA_CHECK_LAUNCH();
+        hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + 255) / 256), dim3(256), 0, stream, M, C, S, ws, gamma, beta, eps, momentum, mean, invstd, scale, shift,
+                           run_mean, run_var, nbt);
+    } else {
+        UIA_CHECK_ARG(run_mean && run_var, "uia_bn_act_fwd: eval mode needs the running buffers");
+        hipLaunchKernelGGL(bn_eval_coeff_kernel, dim3((C + 255) / 256), dim3(256), 0, stream, C, gamma, beta, run_mean, run_var, eps, scale, shift);
+    }
+    UIA_CHECK_LAUNCH();
+    const long n = M * C;
+    if (drop8_ok(d, n, y, out, nullptr)) {
+        const unsigned grid = (unsigned)((n / 8 + 255) / 256);
+        if (dtype == UIA_BF16)
+            hipLaunchKernelGGL(bn_act_apply8_kernel<bf16_t>, dim3(grid), dim3(256), 0, stream, n, C, (const bf16_t*)y, scale, shift, slope, d, (bf16_t*)out);
+        else
+            hipLaunchKernelGGL(bn_act_apply8_kernel<float>, dim3(grid), dim3(256), 0, stream, n, C, (const float*)y, scale, shift, slope, d, (float*)out);
+        UIA_CHECK_LAUNCH();
+        return 0;
+    }
+    if (dtype == UIA_BF16)
+        hipLaunchKernelGGL(bn_act_apply_kernel<bf16_t>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, n, C, (const bf16_t*)y, scale, shift, slope, d, (bf16_t*)out);
+    else
+        hipLaunchKernelGGL(bn_act_apply_kernel<float>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, n, C, (const float*)y, scale, shift, slope, d, (float*)out);
+    UIA_CHECK_LAUNCH();
+    return 0;
+}
+
+int uia_bn_act_bwd_launch(hipStream_t stream, int dtype, long M, int C, const void* y, const void* dout, const float* scale, const float* shift,
+                          const float* mean, const float* invstd, const float* gamma, float* ws, float* dgamma, float* dbeta, void* dy,
+                          float slope, float drop_p, uint64_t seed, const uint8_t* keep_mask) {
+    BN_ARGS_OK("uia_bn_act_bwd");
+    UIA_CHECK_ARG(y && dout && scale && shift && mean && invstd && gamma && ws && dgamma && dbeta && dy, "uia_bn_act_bwd: null tensor");
+    UIA_CHECK_ARG(slope >= 0.f && slope <= 1.f, "uia_bn_act_bwd: slope=%f outside [0, 1]", slope);
+    Drop d;
+    if (drop_of("uia_bn_act_bwd", 1, M * C, drop_p, seed, keep_mask, &d)) return -1;
+    const int S = slices_for(M);
+    if (dtype == UIA_BF16)
+        hipLaunchKernelGGL(reduce_act_bwd_kernel<bf16_t>, dim3(S), dim3(256), 0, stream, M, C, (const bf16_t*)y, (const bf16_t*)dout, scale, shift, mean, invstd, slope, d, ws);
+    else
+        hipLaunchKernelGGL(reduce_act_bwd_kernel<float>, dim3(S), dim3(256), 0, stream, M, C, (const float*)y, (const float*)dout, scale, shift, mean, invstd, slope, d, ws);
+    UIA_CHECK_LAUNCH();
+    hipLaunchKernelGGL(col_finalize_kernel, dim3((C + 255) / 256), dim3(256), 0, stream, C, S, ws, dbeta, dgamma);
+    UIA_CHECK_LAUNCH();
+    const long n = M * C;
+    if (drop8_ok(d, n, y, dout, dy)) {
+        const unsigned grid = (unsigned)((n / 8 + 255) / 256);
+        if (dtype == UIA_BF16)
+            hipLaunchKernelGGL(bn_act_bwd_apply8_kernel<bf16_t>, dim3(grid), dim3(256), 0, stream, M, C, (const bf16_t*)y, (const bf16_t*)dout, scale, shift,
+                               mean, invstd, gamma, dbeta, dgamma, slope, d, (bf16_t*)dy);
+        else
+            hipLaunchKernelGGL(bn_act_bwd_apply8_kernel<float>, dim3(grid), dim3(256), 0, stream, M, C, (const float*)y, (const float*)dout, scale, shift,
+                               mean, invstd, gamma, dbeta, dgamma, slope, d, (float*)dy);
+        UIA_CHECK_LAUNCH();
+        return 0;
+    }
+    if (dtype == UIA_BF16)
+        hipLaunchKernelGGL(bn_act_bwd_apply_kernel<bf16_t>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, M, C, (const bf16_t*)y, (const bf16_t*)dout, scale, shift,
+                           mean, invstd, gamma, dbeta, dgamma, slope, d, (bf16_t*)dy);
+    else
+        hipLaunchKernelGGL(bn_act_bwd_apply_kernel<float>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, M, C, (const float*)y, (const float*)dout, scale, shift,
+                           mean, invstd, gamma, dbeta, dgamma, slope, d, (float*)dy);
     UIA_CHECK_LAUNCH();
     return 0;
 }

@@ -13,14 +13,20 @@
 //                  row n, lands at (2y + di, 2x + dj), channel o, of the [B, 2H, 2W, Cout] output.
 //   UIA_CONVT_BWD  its data gradient: output pixel (y, x) of the H×W grid gathers taps (2y + di, 2x + dj) of the 2H×2W gradient;
 //                  w [Cin][4][Cout].
+//   UIA_CONV1      1x1: one tap, the same pixel, no scatter (the baseline UNet's conv1x1, src/third_party/unet.py:42); w [N][C1].
 // bf16: v_mfma_f32_16x16x32_bf16; fp32 (parity mode): v_mfma_f32_16x16x4_f32 (exact fp32 products, k-ordered).  Workgroup tile 64 n × 128 m,
-// four waves of 64 × 32, LDS rows padded by 16 B.  The MFMA path needs C1, C2 (or the gradient's Cout) multiples of 32 and N a multiple of 4;
-// every other shape (the last block's 2·num_classes channels) takes a direct VALU kernel with the same contract.
+// four waves of 64 × 32, LDS rows padded by 16 B.  The MFMA path needs C1, C2 (or the gradient's Cout) multiples of 8 and N a multiple of 4
+// (uia_conv_igemm_form): with multiples of 32 every 32-wide K step is one tap of one source (the first instantiation, unchanged); otherwise
+// the tap and the source are decoded per 8-element chunk and the last K step is zero-filled past K = taps·Cin (GEN).  Every other shape (the
+// first and last layers' 3 and num_classes channels) takes a direct VALU kernel with the same contract.
 //
 // Weight gradient (uia_conv_wgrad): G[r][col] = Σ_m P[m][r] · Q[m][col] over the pixels, split in S contiguous pixel ranges whose partial
 // products are added in split order by a second launch: no float atomics, two identical calls give identical bits.
 //   UIA_CONV3      P = dy [M][N], Q = the 3x3 gather of cat(x1, x2): G = dW [N][9·Cin].
 //   UIA_CONVT_FWD  P = the 2x2 gather of dy (r = tap·Cout + o), Q = x [M][Cin]: G = dW [4·Cout][Cin].
+//   UIA_CONV1      P = dy [M][N], Q = x [M][C1]: G = dW [N][C1].
+// Its MFMA kernel reads 8-element chunks that must stay inside one tap and one source: channel counts and N multiples of 8
+// (uia_conv_wgrad_form).
 // The bias gradients are column sums of dy (uia_colsum_ordered, unet_bn.hip).
 #include "uia_common.h"
 #include "uia_kernels.h"
@@ -89,7 +95,8 @@ __device__ __forceinline__ f32x4_t mma_k32(const T* A, const T* Bm, int lane, f3
     }
 }
 
-template <typename T>
+// GEN = false: C1, C2 multiples of 32.  GEN = true: multiples of 8, tap and source per chunk, zero fill past K.
+template <typename T, bool GEN>
 __global__ __launch_bounds__(256) void conv_igemm_kernel(Geo g, const T* __restrict__ x1, const T* __restrict__ x2, const T* __restrict__ w,
                                                          const float* __restrict__ bias, T* __restrict__ y1, T* __restrict__ y2) {
     constexpr int R = Lds<T>::ROW;
@@ -122,18 +129,34 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(Geo g, const T* __restr
         for (int b = 0; b < 2; ++b) acc[a][b] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
     for (int k0 = 0; k0 < K; k0 += KC) {
-        const int t = k0 / Cin, c0 = k0 - t * Cin;
-        const bool first = c0 < g.C1;
-        const T* src = first ? x1 : x2;
-        const int ld = first ? g.C1 : g.C2, cs = (first ? c0 : c0 - g.C1) + kq;
+        int t, ld, cs;
+        const T* src;
+        bool kin = true;                       // this thread's chunk lies inside K (always, when K is a multiple of 32)
+        if constexpr (GEN) {
+            kin = k0 + kq < K;
+            const int k = kin ? k0 + kq : 0;
+            t = k / Cin;
+            const int c = k - t * Cin;
+            const bool first = c < g.C1;
+            src = first ? x1 : x2;
+            ld = first ? g.C1 : g.C2;
+            cs = first ? c : c - g.C1;
+        } else {
+            t = k0 / Cin;
+            const int c0 = k0 - t * Cin;
+            const bool first = c0 < g.C1;
+            src = first ? x1 : x2;
+            ld = first ? g.C1 : g.C2;
+            cs = (first ? c0 : c0 - g.C1) + kq;
+        }
         T v[2][8], wv[8];
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
-            const long p = pv[i] ? src_pixel(g, pb[i], py[i], px[i], t) : -1;
+            const long p = pv[i] && kin ? src_pixel(g, pb[i], py[i], px[i], t) : -1;
             if (p >= 0) load_chunk8(src + p * ld + cs, v[i]);
             else zero8(v[i]);
         }
-        if (wn < g.N) load_chunk8(w + (long)wn * K + k0 + kq, wv);
+        if (wn < g.N && kin) load_chunk8(w + (long)wn * K + k0 + kq, wv);
         else zero8(wv);
         __syncthreads();
 #pragma unroll
@@ -243,7 +266,7 @@ __device__ __forceinline__ void q_chunk(const WGeo& g, const T* x1, const T* x2,
 // 8 elements of row m of P starting at column r (CONV3: dy; CONVT: the 2x2 gather of dy, r = tap·Cout + o)
 template <typename T>
 __device__ __forceinline__ void p_chunk(const WGeo& g, const T* dy, int b, int y, int x, long m, int r, T (&v)[8]) {
-    if (g.mode == UIA_CONV3) {
+    if (g.mode != UIA_CONVT_FWD) {
         load_chunk8(dy + m * g.N + r, v);
     } else {
         const int t = r / g.N, o = r - t * g.N;
@@ -325,6 +348,9 @@ __global__ __launch_bounds__(256) void conv_wgrad_direct_kernel(WGeo g, const T*
                 const long pp = ((long)b * g.H + yy) * g.W + xx;
                 q = c < g.C1 ? to_f32(x1[pp * g.C1 + c]) : to_f32(x2[pp * g.C2 + c - g.C1]);
                 p = to_f32(dy[(long)m * g.N + r]);
+            } else if (g.mode == UIA_CONV1) {
+                q = to_f32(x1[(long)m * g.C1 + col]);
+                p = to_f32(dy[(long)m * g.N + r]);
             } else {
                 const int t = r / g.N, o = r - t * g.N;
                 q = to_f32(x1[(long)m * g.C1 + col]);
@@ -351,34 +377,48 @@ bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 }  // namespace
 
+// 1: the matrix-core kernel (for 16-byte-aligned operands), 0: the direct kernel.  Pure functions of the shape; the launchers decide by them.
+int uia_conv_igemm_form(int mode, int C1, int C2, int N, int N1) {
+    if (mode < UIA_CONV3 || mode > UIA_CONV1 || C1 <= 0 || C2 < 0 || N <= 0) return 0;
+    return C1 % 8 == 0 && C2 % 8 == 0 && N % 4 == 0 && N1 % 4 == 0 && (mode != UIA_CONVT_FWD || (N / 4) % 4 == 0);
+}
+int uia_conv_wgrad_form(int mode, int C1, int C2, int N) {
+    if ((mode != UIA_CONV3 && mode != UIA_CONVT_FWD && mode != UIA_CONV1) || C1 <= 0 || C2 < 0 || N <= 0) return 0;
+    return C1 % 8 == 0 && C2 % 8 == 0 && N % 8 == 0;
+}
+
 int uia_conv_igemm_launch(hipStream_t stream, int dtype, int mode, int B, int H, int W, int C1, int C2, const void* x1, const void* x2, int N, int N1,
                           const void* w, const float* bias, void* y1, void* y2) {
     UIA_CHECK_ARG(dtype == UIA_F32 || dtype == UIA_BF16, "uia_conv_igemm: dtype must be UIA_F32 or UIA_BF16");
-    UIA_CHECK_ARG(mode == UIA_CONV3 || mode == UIA_CONVT_FWD || mode == UIA_CONVT_BWD, "uia_conv_igemm: unknown mode %d", mode);
+    UIA_CHECK_ARG(mode == UIA_CONV3 || mode == UIA_CONVT_FWD || mode == UIA_CONVT_BWD || mode == UIA_CONV1, "uia_conv_igemm: unknown mode %d", mode);
     UIA_CHECK_ARG(B > 0 && H > 0 && W > 0 && C1 > 0 && C2 >= 0 && N > 0, "uia_conv_igemm: B=%d H=%d W=%d C1=%d C2=%d N=%d must be positive (C2 >= 0)", B, H, W, C1, C2, N);
     UIA_CHECK_ARG((long)B * H * W * (C1 + C2) * 9 < (1l << 40) && (long)(C1 + C2) * 9 < (1 << 20), "uia_conv_igemm: shape too large");
     UIA_CHECK_ARG(x1 && w && y1, "uia_conv_igemm: null tensor");
-    UIA_CHECK_ARG(mode == UIA_CONV3 || C2 == 0, "uia_conv_igemm: the transposed conv takes one source (C2=%d)", C2);
+    UIA_CHECK_ARG(mode == UIA_CONV3 || C2 == 0, "uia_conv_igemm: the transposed and the 1x1 conv take one source (C2=%d)", C2);
     UIA_CHECK_ARG(C2 == 0 || x2, "uia_conv_igemm: C2=%d with a null second source", C2);
     UIA_CHECK_ARG(mode != UIA_CONVT_FWD || N % 4 == 0, "uia_conv_igemm: transposed conv rows N=%d must be 4·Cout", N);
     if (mode == UIA_CONV3) {
         UIA_CHECK_ARG(N1 > 0 && N1 <= N, "uia_conv_igemm: output split N1=%d outside (0, %d]", N1, N);
         UIA_CHECK_ARG(N1 == N || y2, "uia_conv_igemm: N1=%d < N=%d needs a second output", N1, N);
     } else {
-        UIA_CHECK_ARG(N1 == N, "uia_conv_igemm: the transposed conv has one output (N1 must equal N)");
+        UIA_CHECK_ARG(N1 == N, "uia_conv_igemm: the transposed and the 1x1 conv have one output (N1 must equal N)");
     }
     const int taps = mode == UIA_CONV3 ? 9 : (mode == UIA_CONVT_BWD ? 4 : 1);
     Geo g{mode, B, H, W, C1, C2, N, N1, taps};
     const long M = (long)B * H * W;
     const size_t es = dtype == UIA_BF16 ? 2 : 4;
-    const bool mfma = C1 % KC == 0 && C2 % KC == 0 && N % 4 == 0 && N1 % 4 == 0 && (mode != UIA_CONVT_FWD || (N / 4) % 4 == 0) &&
+    const bool mfma = uia_conv_igemm_form(mode, C1, C2, N, N1) &&
                       aligned16(x1) && aligned16(x2) && aligned16(w) && (((uintptr_t)y1 | (uintptr_t)y2) % (4 * es)) == 0;
     if (mfma) {
         dim3 grid((unsigned)((M + TM - 1) / TM), (unsigned)((N + TN - 1) / TN));
-        if (dtype == UIA_BF16)
-            hipLaunchKernelGGL(conv_igemm_kernel<bf16_t>, grid, dim3(256), 0, stream, g, (const bf16_t*)x1, (const bf16_t*)x2, (const bf16_t*)w, bias, (bf16_t*)y1, (bf16_t*)y2);
-        else
-            hipLaunchKernelGGL(conv_igemm_kernel<float>, grid, dim3(256), 0, stream, g, (const float*)x1, (const float*)x2, (const float*)w, bias, (float*)y1, (float*)y2);
+        const bool gen = C1 % KC != 0 || C2 % KC != 0;
+        if (dtype == UIA_BF16) {
+            auto k = gen ? conv_igemm_kernel<bf16_t, true> : conv_igemm_kernel<bf16_t, false>;
+            hipLaunchKernelGGL(k, grid, dim3(256), 0, stream, g, (const bf16_t*)x1, (const bf16_t*)x2, (const bf16_t*)w, bias, (bf16_t*)y1, (bf16_t*)y2);
+        } else {
+            auto k = gen ? conv_igemm_kernel<float, true> : conv_igemm_kernel<float, false>;
+            hipLaunchKernelGGL(k, grid, dim3(256), 0, stream, g, (const float*)x1, (const float*)x2, (const float*)w, bias, (float*)y1, (float*)y2);
+        }
     } else {
         const long n = M * N;
         dim3 grid((unsigned)((n + 255) / 256));
@@ -391,17 +431,24 @@ int uia_conv_igemm_launch(hipStream_t stream, int dtype, int mode, int B, int H,
     return 0;
 }
 
-static bool wgrad_mfma_shape(int C1, int C2, int N) { return C1 % KC == 0 && C2 % KC == 0 && N % 8 == 0; }
+static bool wgrad_mfma_shape(int mode, int C1, int C2, int N) { return uia_conv_wgrad_form(mode, C1, C2, N) != 0; }
+static int wgrad_rows(int mode, int N) { return mode == UIA_CONVT_FWD ? 4 * N : N; }
+static int wgrad_cols(int mode, int C1, int C2) { return mode == UIA_CONV3 ? 9 * (C1 + C2) : C1; }
 
 int uia_conv_wgrad_splits(int mode, int B, int H, int W, int C1, int C2, int N) {
     const long M = (long)B * H * W;
-    const int R = mode == UIA_CONV3 ? N : 4 * N;
-    const int Cols = mode == UIA_CONV3 ? 9 * (C1 + C2) : C1;
+    const int R = wgrad_rows(mode, N);
+    const int Cols = wgrad_cols(mode, C1, C2);
     long S;
-    if (wgrad_mfma_shape(C1, C2, N)) {
+    if (wgrad_mfma_shape(mode, C1, C2, N)) {
         const long tiles = (long)((Cols + 63) / 64) * ((R + 63) / 64);
-        S = (2 * uia_num_cus() + tiles - 1) / tiles;
-        S = S < 1 ? 1 : (S > UIA_WGRAD_MAX_SPLITS ? UIA_WGRAD_MAX_SPLITS : S);
+        // channel counts below a multiple of 32 are the widest-resolution layers: a handful of tiles over millions of pixels, whose step
+        // (gather, two barriers, four MFMAs) is latency-bound, so several workgroups per CU and a higher cap.  The shapes that always
+        // ran here keep their split count, and with it their bits.
+        const bool narrow = C1 % KC != 0 || C2 % KC != 0;
+        const long cap = narrow ? UIA_WGRAD_MAX_NARROW_SPLITS : UIA_WGRAD_MAX_SPLITS;
+        S = ((narrow ? 8 : 2) * uia_num_cus() + tiles - 1) / tiles;
+        S = S < 1 ? 1 : (S > cap ? cap : S);
     } else {
         // the direct path has few outputs (the last block: 2..4 channels) and a long pixel reduction: spread it over ~8 workgroups per CU
         const long groups = ((long)R * Cols + 63) / 64;
@@ -416,18 +463,18 @@ int uia_conv_wgrad_splits(int mode, int B, int H, int W, int C1, int C2, int N) 
 int uia_conv_wgrad_launch(hipStream_t stream, int dtype, int mode, int B, int H, int W, int C1, int C2, const void* x1, const void* x2, int N,
                           const void* dy, float* ws, float* dw) {
     UIA_CHECK_ARG(dtype == UIA_F32 || dtype == UIA_BF16, "uia_conv_wgrad: dtype must be UIA_F32 or UIA_BF16");
-    UIA_CHECK_ARG(mode == UIA_CONV3 || mode == UIA_CONVT_FWD, "uia_conv_wgrad: mode must be UIA_CONV3 or UIA_CONVT_FWD (got %d)", mode);
+    UIA_CHECK_ARG(mode == UIA_CONV3 || mode == UIA_CONVT_FWD || mode == UIA_CONV1, "uia_conv_wgrad: mode must be UIA_CONV3, UIA_CONVT_FWD or UIA_CONV1 (got %d)", mode);
     UIA_CHECK_ARG(B > 0 && H > 0 && W > 0 && C1 > 0 && C2 >= 0 && N > 0, "uia_conv_wgrad: B=%d H=%d W=%d C1=%d C2=%d N=%d must be positive (C2 >= 0)", B, H, W, C1, C2, N);
-    UIA_CHECK_ARG(mode == UIA_CONV3 || C2 == 0, "uia_conv_wgrad: the transposed conv takes one source (C2=%d)", C2);
+    UIA_CHECK_ARG(mode == UIA_CONV3 || C2 == 0, "uia_conv_wgrad: the transposed and the 1x1 conv take one source (C2=%d)", C2);
     UIA_CHECK_ARG(x1 && dy && dw && (C2 == 0 || x2), "uia_conv_wgrad: null tensor");
     UIA_CHECK_ARG((long)B * 2 * H * 2 * W < (1l << 31), "uia_conv_wgrad: %ld pixels exceed the 32-bit pixel index", (long)B * H * W);
     const int S = uia_conv_wgrad_splits(mode, B, H, W, C1, C2, N);
     UIA_CHECK_ARG(S == 1 || ws, "uia_conv_wgrad: %d splits need scratch (uia_conv_wgrad_splits · R · Cols floats)", S);
     const long M = (long)B * H * W;
-    WGeo g{mode, B, H, W, C1, C2, N, mode == UIA_CONV3 ? N : 4 * N, mode == UIA_CONV3 ? 9 * (C1 + C2) : C1, 0};
+    WGeo g{mode, B, H, W, C1, C2, N, wgrad_rows(mode, N), wgrad_cols(mode, C1, C2), 0};
     g.per = ((M + S - 1) / S + 31) / 32 * 32;
     float* dst = S == 1 ? dw : ws;
-    const bool mfma = wgrad_mfma_shape(C1, C2, N) && aligned16(x1) && aligned16(x2) && aligned16(dy) && aligned16(dst);
+    const bool mfma = wgrad_mfma_shape(mode, C1, C2, N) && aligned16(x1) && aligned16(x2) && aligned16(dy) && aligned16(dst);
     if (mfma) {
         dim3 grid((unsigned)((g.Cols + 63) / 64), (unsigned)((g.R + 63) / 64), (unsigned)S);
         if (dtype == UIA_BF16)

@@ -104,6 +104,12 @@ PROTOTYPES = {
     "uia_conv_igemm": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp]),
     "uia_conv_wgrad_splits": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "uia_conv_wgrad": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, vp]),
+    "uia_conv_igemm_form": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "uia_conv_wgrad_form": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "uia_bn_act_fwd": (C.c_int, [vp, C.c_int, C.c_int, i64, C.c_int, vp, vp, vp, vp, vp, vp, f32, f32, vp, vp, vp, vp, vp, f32, vp, f32, C.c_uint64, vp]),
+    "uia_bn_act_bwd": (C.c_int, [vp, C.c_int, i64, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, f32, f32, C.c_uint64, vp]),
+    "uia_maxpool2_fwd": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
+    "uia_maxpool2_bwd": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
     "uia_bn_fwd": (C.c_int, [vp, C.c_int, C.c_int, i64, C.c_int, vp, vp, vp, vp, vp, vp, f32, f32, vp, vp, vp, vp, vp, C.c_int, vp]),
     "uia_bn_relu_bwd": (C.c_int, [vp, C.c_int, i64, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "uia_colsum_ordered": (C.c_int, [vp, C.c_int, i64, C.c_int, vp, vp, vp]),

@@ -1896,6 +1896,96 @@ class UnetConvBNReLUFn(torch.autograd.Function):
         return dx1, dx2, dw, db, dgamma, dbeta, None, None, None, None, None, None
 
 
+class UnetConvBNActFn(torch.autograd.Function):
+    """Dropout(LeakyReLU(BatchNorm2d(Conv2d3x3(cat[x1, x2]) + b))) on NHWC x1 [B,H,W,C1], x2 [B,H,W,C2] (x2 may be None): one half of the
+    baseline UNet's ConvBlock; the concatenation is never written.  training: batch statistics, running buffers updated on the device,
+    dropout with probability drop_p (keep_mask: an explicit uint8 mask of the output's shape, for tests; otherwise the seed comes from
+    set_dropout_seed as at the other dropout sites and the mask is regenerated in the backward).  eval: running statistics, no dropout
+    (no backward)."""
+
+    @staticmethod
+    def forward(ctx, x1, x2, w, b, gamma, beta, running_mean, running_var, nbt, training, momentum, eps, slope, drop_p, keep_mask):
+        dt = x1.dtype
+        drop_p = float(drop_p)
+        if not 0.0 <= drop_p < 1.0:
+            raise UiaError(f"UnetConvBNActFn: drop_p={drop_p} outside [0, 1)")
+        if keep_mask is not None and tuple(keep_mask.shape) != (*x1.shape[:3], w.shape[0]):
+            raise UiaError(f"UnetConvBNActFn: keep_mask {tuple(keep_mask.shape)}, expected {(*x1.shape[:3], w.shape[0])}")
+        drop = training and drop_p > 0.0
+        seed = _next_seed() if drop and keep_mask is None else 0
+        y = ops.conv_igemm(ops.CONV3, x1, x2, conv3_rows(w, dt), w.shape[0], bias=b.detach().contiguous())
+        out, mean, invstd, scale, shift = ops.bn_act_fwd(y, gamma.detach(), beta.detach(), running_mean, running_var, nbt, training, momentum, eps, slope,
+                                                         drop_p if drop else 0.0, seed, keep_mask if drop else None)
+        if training:
+            ctx.save_for_backward(x1, x2, w, y, gamma, mean, invstd, scale, shift, keep_mask if drop else None)
+        ctx.training, ctx.act = training, (float(slope), drop_p if drop else 0.0, seed)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        if not ctx.training:
+            raise UiaError("UnetConvBNActFn: eval-mode BatchNorm has no backward here (the UNet trains in train mode)")
+        x1, x2, w, y, gamma, mean, invstd, scale, shift, keep_mask = ctx.saved_tensors
+        slope, drop_p, seed = ctx.act
+        dy, dgamma, dbeta = ops.bn_act_bwd(y, dout.contiguous(), scale, shift, mean, invstd, gamma.detach(), slope, drop_p, seed, keep_mask)
+        N, Cin = w.shape[0], w.shape[1]
+        dw = ops.conv_wgrad(ops.CONV3, x1, x2, dy, N).reshape(N, 3, 3, Cin).permute(0, 3, 1, 2).contiguous()
+        db = ops.colsum_ordered(dy)
+        dx1 = dx2 = None
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            C1 = x1.shape[3]
+            r = ops.conv_igemm(ops.CONV3, dy, None, conv3_dgrad_rows(w, dy.dtype), Cin, n1=C1)
+            dx1, dx2 = (r if x2 is not None else (r, None))
+        return dx1, dx2, dw, db, dgamma, dbeta, None, None, None, None, None, None, None, None, None
+
+
+class UnetConvFn(torch.autograd.Function):
+    """Conv2d 3x3 (pad 1) or 1x1 with bias and no norm on NHWC x [B,H,W,Cin] -> [B,H,W,Cout]: the baseline UNet's out_conv and conv1x1.
+    w [Cout, Cin, k, k] as nn.Conv2d keeps it, k in (1, 3)."""
+
+    @staticmethod
+    def forward(ctx, x, w, b):
+        k = w.shape[2]
+        if k not in (1, 3) or w.shape[3] != k:
+            raise UiaError(f"UnetConvFn: kernel {tuple(w.shape[2:])} is not 1x1 or 3x3")
+        dt = x.dtype
+        ctx.save_for_backward(x, w)
+        if k == 3:
+            return ops.conv_igemm(ops.CONV3, x, None, conv3_rows(w, dt), w.shape[0], bias=b.detach().contiguous())
+        return ops.conv_igemm(ops.CONV1, x, None, w.detach().reshape(w.shape[0], w.shape[1]).to(dt).contiguous(), w.shape[0], bias=b.detach().contiguous())
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w = ctx.saved_tensors
+        dy = dy.contiguous()
+        N, Cin, k = w.shape[0], w.shape[1], w.shape[2]
+        db = ops.colsum_ordered(dy)
+        dx = None
+        if k == 3:
+            dw = ops.conv_wgrad(ops.CONV3, x, None, dy, N).reshape(N, 3, 3, Cin).permute(0, 3, 1, 2).contiguous()
+            if ctx.needs_input_grad[0]:
+                dx = ops.conv_igemm(ops.CONV3, dy, None, conv3_dgrad_rows(w, dy.dtype), Cin)
+        else:
+            dw = ops.conv_wgrad(ops.CONV1, x, None, dy, N).reshape(N, Cin, 1, 1)
+            if ctx.needs_input_grad[0]:
+                dx = ops.conv_igemm(ops.CONV1, dy, None, w.detach().reshape(N, Cin).t().to(dy.dtype).contiguous(), Cin)
+        return dx, dw, db
+
+
+class MaxPool2Fn(torch.autograd.Function):
+    """nn.MaxPool2d(2) on NHWC; the backward recomputes the argmax from the saved input."""
+
+    @staticmethod
+    def forward(ctx, x):
+        ctx.save_for_backward(x)
+        return ops.maxpool2(x)
+
+    @staticmethod
+    def backward(ctx, dy):
+        (x,) = ctx.saved_tensors
+        return ops.maxpool2_bwd(x, dy.contiguous())
+
+
 class UnetConvTransposeFn(torch.autograd.Function):
     """ConvTranspose2d(k=2, s=2) on NHWC x [B,h,w,Cin] -> [B,2h,2w,Cout]; weight [Cin, Cout, 2, 2] as nn.ConvTranspose2d keeps it."""
 

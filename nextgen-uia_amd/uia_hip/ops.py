@@ -1626,7 +1626,7 @@ def surface_distances(logits, label, percentile=95.0):
 
 
 # ---------------------------------------------------------------- DINOv2 UNet decoder (csrc/unet_conv.hip, unet_bn.hip, unet_resample.hip)
-CONV3, CONVT_FWD, CONVT_BWD = 0, 1, 2      # uia_conv_igemm / uia_conv_wgrad modes
+CONV3, CONVT_FWD, CONVT_BWD, CONV1 = 0, 1, 2, 3      # uia_conv_igemm / uia_conv_wgrad modes
 BN_SLICES = 256                            # UIA_BN_SLICES
 
 
@@ -1640,7 +1640,10 @@ def _nhwc(t, name, dt=None):
 
 def conv_igemm(mode, x1, x2, w, n, bias=None, n1=None):
     """uia_conv_igemm.  CONV3: x1 [B,H,W,C1] (+ x2 [B,H,W,C2]) NHWC, w [n, 9·(C1+C2)] -> y [B,H,W,n], or (y1, y2) split at channel n1.
-    CONVT_FWD: x1 [B,h,w,Cin], w [4·Cout, Cin], n = 4·Cout -> [B,2h,2w,Cout].  CONVT_BWD: x1 = dy [B,2h,2w,Cout], w [Cin, 4·Cout], n = Cin -> [B,h,w,Cin]."""
+    CONVT_FWD: x1 [B,h,w,Cin], w [4·Cout, Cin], n = 4·Cout -> [B,2h,2w,Cout].  CONVT_BWD: x1 = dy [B,2h,2w,Cout], w [Cin, 4·Cout], n = Cin -> [B,h,w,Cin].
+    CONV1: x1 [B,H,W,C1], w [n, C1] -> [B,H,W,n] (its data gradient: the same call on dy with the transposed weight)."""
+    if mode not in (CONV3, CONVT_FWD, CONVT_BWD, CONV1):
+        raise UiaError(f"conv_igemm: unknown mode {mode}")
     _nhwc(x1, "conv_igemm x1")
     dt = x1.dtype
     B, H, W, C1 = x1.shape
@@ -1654,7 +1657,7 @@ def conv_igemm(mode, x1, x2, w, n, bias=None, n1=None):
         H, W = H // 2, W // 2
         if tuple(x1.shape[1:3]) != (2 * H, 2 * W):
             raise UiaError("conv_igemm: the transposed conv's gradient grid must be even")
-    taps = {CONV3: 9, CONVT_FWD: 1, CONVT_BWD: 4}[mode]
+    taps = {CONV3: 9, CONVT_FWD: 1, CONVT_BWD: 4, CONV1: 1}[mode]
     if w.dtype != dt or not w.is_contiguous() or tuple(w.shape) != (n, taps * (C1 + C2)):
         raise UiaError(f"conv_igemm: w must be contiguous {dt} [{n}, {taps * (C1 + C2)}], got {w.dtype} {tuple(w.shape)}")
     if bias is not None:
@@ -1672,7 +1675,10 @@ def conv_igemm(mode, x1, x2, w, n, bias=None, n1=None):
 
 
 def conv_wgrad(mode, x1, x2, dy, n):
-    """uia_conv_wgrad -> fp32 dW.  CONV3: dy [B,H,W,n] -> [n, 9·(C1+C2)].  CONVT_FWD: x1 [B,h,w,Cin], dy [B,2h,2w,n = Cout] -> [4·n, Cin]."""
+    """uia_conv_wgrad -> fp32 dW.  CONV3: dy [B,H,W,n] -> [n, 9·(C1+C2)].  CONVT_FWD: x1 [B,h,w,Cin], dy [B,2h,2w,n = Cout] -> [4·n, Cin].
+    CONV1: dy [B,H,W,n] -> [n, C1]."""
+    if mode not in (CONV3, CONVT_FWD, CONV1):
+        raise UiaError(f"conv_wgrad: unknown mode {mode}")
     _nhwc(x1, "conv_wgrad x1")
     _nhwc(dy, "conv_wgrad dy", x1.dtype)
     B, H, W, C1 = x1.shape
@@ -1680,15 +1686,25 @@ def conv_wgrad(mode, x1, x2, dy, n):
     if x2 is not None:
         _nhwc(x2, "conv_wgrad x2", x1.dtype)
         C2 = x2.shape[3]
-    want = (B, H, W, n) if mode == CONV3 else (B, 2 * H, 2 * W, n)
+    want = (B, 2 * H, 2 * W, n) if mode == CONVT_FWD else (B, H, W, n)
     if tuple(dy.shape) != want:
         raise UiaError(f"conv_wgrad: dy {tuple(dy.shape)}, expected {want}")
-    rows, cols = (n, 9 * (C1 + C2)) if mode == CONV3 else (4 * n, C1)
+    rows, cols = {CONV3: (n, 9 * (C1 + C2)), CONVT_FWD: (4 * n, C1), CONV1: (n, C1)}[mode]
     S = lib().uia_conv_wgrad_splits(mode, B, H, W, C1, C2, n)
     ws = torch.empty(S * rows * cols, device=x1.device, dtype=torch.float32) if S > 1 else None
     dw = torch.empty(rows, cols, device=x1.device, dtype=torch.float32)
     check(lib().uia_conv_wgrad(_stream(), _code(x1.dtype), mode, B, H, W, C1, C2, _p(x1), _p(x2), n, _p(dy), _p(ws), _p(dw)), "uia_conv_wgrad")
     return dw
+
+
+def conv_igemm_form(mode, c1, c2, n, n1=None):
+    """1 when uia_conv_igemm takes the matrix-core kernel for this shape (16-byte-aligned operands), 0 for the direct kernel.  No GPU needed."""
+    return int(lib().uia_conv_igemm_form(int(mode), int(c1), int(c2), int(n), int(n if n1 is None else n1)))
+
+
+def conv_wgrad_form(mode, c1, c2, n):
+    """1 when uia_conv_wgrad takes the matrix-core kernel for this shape (16-byte-aligned operands), 0 for the direct kernel.  No GPU needed."""
+    return int(lib().uia_conv_wgrad_form(int(mode), int(c1), int(c2), int(n)))
 
 
 def colsum_ordered(y):
@@ -1742,6 +1758,93 @@ def bn_relu_bwd(y, dout, scale, shift, mean, invstd, gamma):
     check(lib().uia_bn_relu_bwd(_stream(), _code(y.dtype), M, C, _p(y), _p(dout), _p(scale), _p(shift), _p(mean), _p(invstd), _p(gamma), _p(ws),
                                 _p(dgamma), _p(dbeta), _p(dy)), "uia_bn_relu_bwd")
     return dy, dgamma, dbeta
+
+
+def _keep_mask(keep_mask, y, name):
+    if keep_mask is None:
+        return None
+    if keep_mask.dtype != torch.uint8 or not keep_mask.is_contiguous() or keep_mask.shape != y.shape or keep_mask.device != y.device:
+        raise UiaError(f"{name}: keep_mask must be contiguous uint8 of shape {tuple(y.shape)} on {y.device}, got {keep_mask.dtype} {tuple(keep_mask.shape)}")
+    return keep_mask
+
+
+def _drop_args(name, y, drop_p, keep_mask, training=True):
+    drop_p = float(drop_p)
+    if not 0.0 <= drop_p < 1.0:
+        raise UiaError(f"{name}: drop_p={drop_p} outside [0, 1)")
+    keep_mask = _keep_mask(keep_mask, y, name)
+    if training and drop_p > 0.0 and keep_mask is None and y.numel() % 8:
+        raise UiaError(f"{name}: the generated mask needs a multiple of 8 elements, got {y.numel()}")
+    return drop_p, keep_mask
+
+
+def bn_act_fwd(y, gamma, beta, running_mean, running_var, num_batches_tracked, training, momentum=0.1, eps=1e-5, slope=0.01, drop_p=0.0, seed=0,
+               keep_mask=None):
+    """BatchNorm2d + LeakyReLU(slope) + Dropout(drop_p) on NHWC y (uia_bn_act_fwd).  Returns (out, mean, invstd, scale, shift) as bn_fwd does.
+    Dropout runs in training only: keep_mask (uint8, y's shape) when given, else the draw of ops.dropout for `seed`."""
+    _nhwc(y, "bn_act_fwd y")
+    C = y.shape[3]
+    M = y.numel() // C
+    for t, nm in ((gamma, "gamma"), (beta, "beta"), (running_mean, "running_mean"), (running_var, "running_var")):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != C):
+            raise UiaError(f"bn_act_fwd: {nm} must be contiguous fp32 [{C}]")
+    if num_batches_tracked is not None and num_batches_tracked.dtype != torch.int64:
+        raise UiaError("bn_act_fwd: num_batches_tracked must be int64")
+    drop_p, keep_mask = _drop_args("bn_act_fwd", y, drop_p, keep_mask, training)
+    f = lambda: torch.empty(C, device=y.device, dtype=torch.float32)   # noqa: E731
+    scale, shift = f(), f()
+    mean, invstd, ws = (f(), f(), torch.empty(BN_SLICES * C * 3, device=y.device, dtype=torch.float32)) if training else (None, None, None)
+    out = torch.empty_like(y)
+    check(lib().uia_bn_act_fwd(_stream(), _code(y.dtype), int(bool(training)), M, C, _p(y), _p(gamma), _p(beta), _p(running_mean), _p(running_var),
+                               _p(num_batches_tracked), float(momentum), float(eps), _p(ws), _p(mean), _p(invstd), _p(scale), _p(shift), float(slope), _p(out),
+                               drop_p, int(seed) & 0xFFFFFFFFFFFFFFFF, _p(keep_mask)), "uia_bn_act_fwd")
+    return out, mean, invstd, scale, shift
+
+
+def bn_act_bwd(y, dout, scale, shift, mean, invstd, gamma, slope=0.01, drop_p=0.0, seed=0, keep_mask=None):
+    """Backward of train-mode bn_act_fwd (uia_bn_act_bwd): returns (dy, dgamma, dbeta)."""
+    _nhwc(y, "bn_act_bwd y")
+    _nhwc(dout, "bn_act_bwd dout", y.dtype)
+    if dout.shape != y.shape:
+        raise UiaError("bn_act_bwd: dout and y differ in shape")
+    C = y.shape[3]
+    for t, nm in ((scale, "scale"), (shift, "shift"), (mean, "mean"), (invstd, "invstd"), (gamma, "gamma")):
+        if t is None or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != C:
+            raise UiaError(f"bn_act_bwd: {nm} must be contiguous fp32 [{C}]")
+    drop_p, keep_mask = _drop_args("bn_act_bwd", y, drop_p, keep_mask)
+    M = y.numel() // C
+    ws = torch.empty(BN_SLICES * C * 3, device=y.device, dtype=torch.float32)
+    dgamma = torch.empty(C, device=y.device, dtype=torch.float32)
+    dbeta = torch.empty(C, device=y.device, dtype=torch.float32)
+    dy = torch.empty_like(y)
+    check(lib().uia_bn_act_bwd(_stream(), _code(y.dtype), M, C, _p(y), _p(dout), _p(scale), _p(shift), _p(mean), _p(invstd), _p(gamma), _p(ws),
+                               _p(dgamma), _p(dbeta), _p(dy), float(slope), drop_p, int(seed) & 0xFFFFFFFFFFFFFFFF, _p(keep_mask)), "uia_bn_act_bwd")
+    return dy, dgamma, dbeta
+
+
+def maxpool2(x):
+    """nn.MaxPool2d(2) on NHWC x [B,H,W,C] -> [B,H//2,W//2,C] (uia_maxpool2_fwd); a trailing odd row / column is ignored."""
+    _nhwc(x, "maxpool2")
+    B, H, W, C = x.shape
+    if H < 2 or W < 2:
+        raise UiaError(f"maxpool2: a grid of at least 2x2 is required, got {H}x{W}")
+    y = torch.empty(B, H // 2, W // 2, C, device=x.device, dtype=x.dtype)
+    check(lib().uia_maxpool2_fwd(_stream(), _code(x.dtype), B, H, W, C, _p(x), _p(y)), "uia_maxpool2_fwd")
+    return y
+
+
+def maxpool2_bwd(x, dy):
+    """Backward of maxpool2 (uia_maxpool2_bwd): the argmax is recomputed from x; every element of dx [B,H,W,C] is written."""
+    _nhwc(x, "maxpool2_bwd x")
+    _nhwc(dy, "maxpool2_bwd dy", x.dtype)
+    B, H, W, C = x.shape
+    if H < 2 or W < 2:
+        raise UiaError(f"maxpool2_bwd: a grid of at least 2x2 is required, got {H}x{W}")
+    if tuple(dy.shape) != (B, H // 2, W // 2, C):
+        raise UiaError(f"maxpool2_bwd: dy {tuple(dy.shape)}, expected {(B, H // 2, W // 2, C)}")
+    dx = torch.empty_like(x)
+    check(lib().uia_maxpool2_bwd(_stream(), _code(x.dtype), B, H, W, C, _p(x), _p(dy), _p(dx)), "uia_maxpool2_bwd")
+    return dx
 
 
 def upsample_ac(x, f, backward=False):
