@@ -604,6 +604,57 @@ int uia_resize_aa(void* stream, int dtype, int backward, int B, int C, int Hi, i
                   const float* dout, void* dx);
 
 /* ---------------------------------------------------------------------------------------------
+ * ResNet classification baseline (src/third_party/resnet.py): what a CNN other than a UNet needs, under the conventions of the section
+ * above (NHWC, bf16 / fp32, fixed reduction orders, no float atomics, no memset: two identical calls give identical bits).
+ *
+ * uia_conv_strided: Conv2d(k, stride s, padding k/2, bias=False), k in {1, 3, 7}, s in {1, 2}, of x [B,H,W,C] with N output channels on the
+ *   output grid Ho×Wo, Ho = (H − 1)/s + 1 (floor; odd and even H, W).  H, W and C always name the conv's INPUT, N its output.
+ *   dgrad = 0  forward: x [B,H,W,C], w [N][k²·C] (column (ky·k + kx)·C + c) -> y [B,Ho,Wo,N].
+ *   dgrad = 1  data gradient: x = dy [B,Ho,Wo,N], w [C][k²·N] (column (ky·k + kx)·N + n, taps not flipped) -> y = dx [B,H,W,C]: input pixel
+ *              (y, x) takes tap (ky, kx) where y + k/2 − ky and x + k/2 − kx are divisible by s and the quotient lies in Ho×Wo.  Every
+ *              tap runs; the invalid ones contribute zeros.
+ *   MFMA path (the 64×128 tile of uia_conv_igemm) when C % 8 == 0, N % 8 == 0 and the operands are 16-byte aligned; a direct kernel otherwise.
+ * uia_conv_strided_wgrad: fp32 dw [N][k²·C] from x [B,H,W,C] and dy [B,Ho,Wo,N] over the B·Ho·Wo output pixels, in
+ *   uia_conv_strided_wgrad_splits(...) pixel ranges added in range order (the rule of uia_conv_wgrad_splits, the narrow-channel cap
+ *   included).  ws: splits·N·k²·C floats when splits > 1.
+ * uia_conv_strided_form / uia_conv_strided_wgrad_form: 1 when the matrix-core kernel is taken for 16-byte-aligned operands, else 0 (pure
+ *   functions of the shape, callable without a GPU; the launchers decide by them).  Any other k or s is refused by the launchers.
+ * The 7×7 stem (3 -> 64) runs on the MFMA path with 8 input channels, channels 3..7 zero: uia_nchw_to_nhwc packs the image and the weight. */
+int uia_conv_strided(void* stream, int dtype, int dgrad, int B, int H, int W, int C, int k, int s, const void* x, int N, const void* w, void* y);
+int uia_conv_strided_wgrad_splits(int B, int H, int W, int C, int k, int s, int N);
+int uia_conv_strided_form(int dgrad, int C, int N, int k, int s);
+int uia_conv_strided_wgrad_form(int C, int N, int k, int s);
+int uia_conv_strided_wgrad(void* stream, int dtype, int B, int H, int W, int C, int k, int s, const void* x, int N, const void* dy, float* ws,
+                           float* dw);
+/* nn.MaxPool2d(kernel 3, stride 2, padding 1) on NHWC x [B,H,W,C] -> y [B,Ho,Wo,C], Ho = (H − 1)/2 + 1.  The padding is −inf, not 0: an
+ *   all-negative window returns its maximum.  Backward: a gather with no atomics; each input pixel recomputes the argmax of the at most
+ *   four windows that cover it (ties to the first maximum in row-major window order, as PyTorch), adds dy of the windows it wins in window
+ *   order (fp32, rounded once) and writes every element of dx [B,H,W,C].  16-byte accesses when the channel count and the pointers allow,
+ *   a scalar form otherwise.  Inputs are finite: the ordering of NaN is not part of the contract. */
+int uia_maxpool3s2_fwd(void* stream, int dtype, int B, int H, int W, int C, const void* x, void* y);
+int uia_maxpool3s2_bwd(void* stream, int dtype, int B, int H, int W, int C, const void* x, const void* dy, void* dx);
+/* BatchNorm2d + residual add + ReLU, out = relu(y·scale + shift + r), on the arguments of uia_bn_fwd / uia_bn_relu_bwd.  Statistics, running
+ *   buffers and scale / shift are exactly uia_bn_fwd's; r [M, C] (dtype) may be null, and then the result is uia_bn_fwd(relu = 1) bit for bit.
+ *   uia_bn_add_relu_bwd takes the forward's out instead of scale / shift: dz = dout·[out > 0] (out == 0 takes 0), dr = dz (its own tensor,
+ *   may be null), then the training-mode BatchNorm backward of uia_bn_relu_bwd on dz.  ws: UIA_BN_SLICES·C·3 floats.
+ *   The downsample branch's BatchNorm without activation is uia_bn_act_fwd / uia_bn_act_bwd with slope = 1, drop_p = 0. */
+int uia_bn_add_relu_fwd(void* stream, int dtype, int training, int64_t M, int C, const void* y, const void* r, const float* gamma, const float* beta,
+                        float* running_mean, float* running_var, int64_t* num_batches_tracked, float momentum, float eps, float* ws, float* mean,
+                        float* invstd, float* scale, float* shift, void* out);
+int uia_bn_add_relu_bwd(void* stream, int dtype, int64_t M, int C, const void* y, const void* out, const void* dout, const float* mean,
+                        const float* invstd, const float* gamma, float* ws, float* dgamma, float* dbeta, void* dy, void* dr);
+/* Global average pool of NHWC x [B,H,W,C] (dtype) -> pooled [B,C] fp32: the H·W pixels added in pixel order in fp32, divided once; one
+ *   launch.  Backward: dx[b,y,x,c] = dout[b,c]/(H·W) (dtype), one launch. */
+int uia_avgpool_fwd(void* stream, int dtype, int B, int H, int W, int C, const void* x, float* pooled);
+int uia_avgpool_bwd(void* stream, int dtype, int B, int H, int W, int C, const float* dout, void* dx);
+/* Layout helper: fp32 NCHW x [B,Cin,H,W] -> NHWC out [B,H,W,Cout] (dtype).  Output channel c < rep copies input channel c (Cin == 1: input
+ *   channel 0 for every c < rep, the widening of a one-channel batch); channels rep..Cout−1 are zero.  The stem's image (rep 3, Cout 8)
+ *   and its weight [64,3,7,7] -> [64][49][8] (B = 64, H = W = 7) both pass through it.
+ * uia_add2: out = a + b element-wise (fp32 sum rounded once; out may alias a or b): the sum of a block's two input gradients. */
+int uia_nchw_to_nhwc(void* stream, int dtype, int B, int Cin, int H, int W, int Cout, int rep, const float* x, void* out);
+int uia_add2(void* stream, int dtype, int64_t n, const void* a, const void* b, void* out);
+
+/* ---------------------------------------------------------------------------------------------
  * Data-parallel exchange (new: the reference is single-process, finetune.py:287-302 accumulates
  * instead).  RCCL all-reduce on the caller's stream; the unique id travels through the host.
  * Every RCCL failure is reported as "rank r/world: <call> failed: <reason>" through uia_last_error(). */

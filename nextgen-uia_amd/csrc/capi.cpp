@@ -272,6 +272,41 @@ int uia_maxpool2_fwd(void* stream, int dtype, int B, int H, int W, int C, const 
 int uia_maxpool2_bwd(void* stream, int dtype, int B, int H, int W, int C, const void* x, const void* dy, void* dx) {
     return uia_maxpool2_launch((hipStream_t)stream, dtype, 1, B, H, W, C, x, dy, dx);
 }
+int uia_conv_strided(void* stream, int dtype, int dgrad, int B, int H, int W, int C, int k, int s, const void* x, int N, const void* w, void* y) {
+    return uia_conv_strided_launch((hipStream_t)stream, dtype, dgrad, B, H, W, C, k, s, x, N, w, y);
+}
+int uia_conv_strided_wgrad(void* stream, int dtype, int B, int H, int W, int C, int k, int s, const void* x, int N, const void* dy, float* ws,
+                           float* dw) {
+    return uia_conv_strided_wgrad_launch((hipStream_t)stream, dtype, B, H, W, C, k, s, x, N, dy, ws, dw);
+}
+int uia_maxpool3s2_fwd(void* stream, int dtype, int B, int H, int W, int C, const void* x, void* y) {
+    return uia_maxpool3s2_launch((hipStream_t)stream, dtype, 0, B, H, W, C, x, nullptr, y);
+}
+int uia_maxpool3s2_bwd(void* stream, int dtype, int B, int H, int W, int C, const void* x, const void* dy, void* dx) {
+    return uia_maxpool3s2_launch((hipStream_t)stream, dtype, 1, B, H, W, C, x, dy, dx);
+}
+int uia_bn_add_relu_fwd(void* stream, int dtype, int training, int64_t M, int C, const void* y, const void* r, const float* gamma, const float* beta,
+                        float* running_mean, float* running_var, int64_t* num_batches_tracked, float momentum, float eps, float* ws, float* mean,
+                        float* invstd, float* scale, float* shift, void* out) {
+    return uia_bn_add_relu_fwd_launch((hipStream_t)stream, dtype, training, (long)M, C, y, r, gamma, beta, running_mean, running_var, num_batches_tracked,
+                                      momentum, eps, ws, mean, invstd, scale, shift, out);
+}
+int uia_bn_add_relu_bwd(void* stream, int dtype, int64_t M, int C, const void* y, const void* out, const void* dout, const float* mean,
+                        const float* invstd, const float* gamma, float* ws, float* dgamma, float* dbeta, void* dy, void* dr) {
+    return uia_bn_add_relu_bwd_launch((hipStream_t)stream, dtype, (long)M, C, y, out, dout, mean, invstd, gamma, ws, dgamma, dbeta, dy, dr);
+}
+int uia_avgpool_fwd(void* stream, int dtype, int B, int H, int W, int C, const void* x, float* pooled) {
+    return uia_avgpool_launch((hipStream_t)stream, dtype, 0, B, H, W, C, x, pooled, nullptr);
+}
+int uia_avgpool_bwd(void* stream, int dtype, int B, int H, int W, int C, const float* dout, void* dx) {
+    return uia_avgpool_launch((hipStream_t)stream, dtype, 1, B, H, W, C, nullptr, const_cast<float*>(dout), dx);
+}
+int uia_nchw_to_nhwc(void* stream, int dtype, int B, int Cin, int H, int W, int Cout, int rep, const float* x, void* out) {
+    return uia_nchw_to_nhwc_launch((hipStream_t)stream, dtype, B, Cin, H, W, Cout, rep, x, out);
+}
+int uia_add2(void* stream, int dtype, int64_t n, const void* a, const void* b, void* out) {
+    return uia_add2_launch((hipStream_t)stream, dtype, (long)n, a, b, out);
+}
 int uia_upsample_ac(void* stream, int dtype, int backward, int B, int H, int W, int C, int f, const void* in, void* out) {
     return uia_upsample_ac_launch((hipStream_t)stream, dtype, backward, B, H, W, C, f, in, out);
 }

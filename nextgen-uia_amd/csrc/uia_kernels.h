@@ -107,6 +107,22 @@ int uia_bn_act_bwd_launch(hipStream_t stream, int dtype, long M, int C, const vo
                           const float* mean, const float* invstd, const float* gamma, float* ws, float* dgamma, float* dbeta, void* dy,
                           float slope, float drop_p, uint64_t seed, const uint8_t* keep_mask);
 int uia_maxpool2_launch(hipStream_t stream, int dtype, int backward, int B, int H, int W, int C, const void* x, const void* dy, void* out);
+int uia_conv_strided_launch(hipStream_t stream, int dtype, int dgrad, int B, int H, int W, int C, int k, int s, const void* x, int N, const void* w,
+                            void* y);
+int uia_conv_strided_wgrad_splits(int B, int H, int W, int C, int k, int s, int N);
+int uia_conv_strided_form(int dgrad, int C, int N, int k, int s);
+int uia_conv_strided_wgrad_form(int C, int N, int k, int s);
+int uia_conv_strided_wgrad_launch(hipStream_t stream, int dtype, int B, int H, int W, int C, int k, int s, const void* x, int N, const void* dy,
+                                  float* ws, float* dw);
+int uia_maxpool3s2_launch(hipStream_t stream, int dtype, int backward, int B, int H, int W, int C, const void* x, const void* dy, void* out);
+int uia_avgpool_launch(hipStream_t stream, int dtype, int backward, int B, int H, int W, int C, const void* x, float* pooled, void* dx);
+int uia_nchw_to_nhwc_launch(hipStream_t stream, int dtype, int B, int Cin, int H, int W, int Cout, int rep, const float* x, void* out);
+int uia_add2_launch(hipStream_t stream, int dtype, long n, const void* a, const void* b, void* out);
+int uia_bn_add_relu_fwd_launch(hipStream_t stream, int dtype, int training, long M, int C, const void* y, const void* r, const float* gamma,
+                               const float* beta, float* run_mean, float* run_var, int64_t* nbt, float momentum, float eps, float* ws, float* mean,
+                               float* invstd, float* scale, float* shift, void* out);
+int uia_bn_add_relu_bwd_launch(hipStream_t stream, int dtype, long M, int C, const void* y, const void* out, const void* dout, const float* mean,
+                               const float* invstd, const float* gamma, float* ws, float* dgamma, float* dbeta, void* dy, void* dr);
 int uia_upsample_ac_launch(hipStream_t stream, int dtype, int backward, int B, int H, int W, int C, int f, const void* in, void* out);
 int uia_resize_aa_launch(hipStream_t stream, int dtype, int backward, int B, int C, int Hi, int Wi, int Ho, int Wo, const void* x, float* tmp, float* out,
                          const float* dout, void* dx);

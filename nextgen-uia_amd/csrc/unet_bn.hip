@@ -473,3 +473,131 @@ int uia_bn_act_bwd_launch(hipStream_t stream, int dtype, long M, int C, const vo
     UIA_CHECK_LAUNCH();
     return 0;
 }
+
+// ---------------------------------------------------------------- BatchNorm + residual add + ReLU (the ResNet baseline's BasicBlock tail)
+// out = relu(y·scale + shift + r); statistics, running buffers and scale / shift are uia_bn_fwd's (the same launches).  With r null the
+// apply is bn_apply_kernel(relu = 1)'s arithmetic: the same bits.  Backward: dz = dout·[out > 0] (out == 0 takes 0, as uia_bn_relu_bwd at
+// z == 0), dr = dz in the tensors' dtype, then the training-mode BatchNorm backward on dz with the reductions of reduce_kernel<RED_BWD>.
+namespace {
+
+template <typename T>
+__global__ __launch_bounds__(256) void bn_add_relu_apply_kernel(long n, int C, const T* __restrict__ y, const T* __restrict__ r, const float* __restrict__ scale,
+                                                                const float* __restrict__ shift, T* __restrict__ out) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int c = (int)(i % C);
+    float v = fmaf(to_f32(y[i]), scale[c], shift[c]);
+    if (r) v += to_f32(r[i]);
+    v = v > 0.f ? v : 0.f;
+    out[i] = from_f32<T>(v);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void reduce_add_relu_bwd_kernel(long M, int C, const T* __restrict__ y, const T* __restrict__ outv, const T* __restrict__ dout,
+                                                                  const float* __restrict__ mean, const float* __restrict__ invstd, float* __restrict__ ws) {
+    __shared__ float red[2][256];
+    const int S = gridDim.x, s = blockIdx.x, tid = threadIdx.x;
+    const long per = (M + S - 1) / S;
+    const long rb = (long)s * per, re = rb + per < M ? rb + per : M;
+    const int Cb = C < 256 ? C : 256, RP = 256 / Cb;
+    for (int cbase = 0; cbase < C; cbase += Cb) {
+        const int c = cbase + tid % Cb, rl = tid / Cb;
+        const bool act = rl < RP && c < C;
+        float a = 0.f, q = 0.f;
+        if (act && rb < re) {
+            const float mu = mean[c], is = invstd[c];
+            for (long r = rb + rl; r < re; r += RP) {
+                const float dz = to_f32(outv[r * C + c]) > 0.f ? to_f32(dout[r * C + c]) : 0.f;
+                a += dz;
+                q = fmaf(dz, (to_f32(y[r * C + c]) - mu) * is, q);
+            }
+        }
+        red[0][tid] = a;
+        red[1][tid] = q;
+        __syncthreads();
+        if (rl == 0 && c < C) {
+            for (int k = 1; k < RP; ++k) {
+                a += red[0][tid + k * Cb];
+                q += red[1][tid + k * Cb];
+            }
+            float* o = ws + ((size_t)s * C + c) * 3;
+            o[0] = a;
+            o[1] = q;
+            o[2] = 0.f;
+        }
+        __syncthreads();
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void bn_add_relu_bwd_apply_kernel(long M, int C, const T* __restrict__ y, const T* __restrict__ outv, const T* __restrict__ dout,
+                                                                    const float* __restrict__ mean, const float* __restrict__ invstd, const float* __restrict__ gamma,
+                                                                    const float* __restrict__ dbeta, const float* __restrict__ dgamma, T* __restrict__ dy,
+                                                                    T* __restrict__ dr) {
+    const long i = (long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= M * C) return;
+    const int c = (int)(i % C);
+    const T g = dout[i];
+    const bool on = to_f32(outv[i]) > 0.f;
+    const float dz = on ? to_f32(g) : 0.f;
+    if (dr) dr[i] = on ? g : (T)0.f;
+    dy[i] = from_f32<T>(bn_bwd_elem(to_f32(y[i]), dz, mean[c], invstd[c], gamma[c], dbeta[c], dgamma[c], 1.0f / (float)M));
+}
+
+}  // namespace
+
+int uia_bn_add_relu_fwd_launch(hipStream_t stream, int dtype, int training, long M, int C, const void* y, const void* r, const float* gamma,
+                               const float* beta, float* run_mean, float* run_var, int64_t* nbt, float momentum, float eps, float* ws, float* mean,
+                               float* invstd, float* scale, float* shift, void* out) {
+    BN_ARGS_OK("uia_bn_add_relu_fwd");
+    UIA_CHECK_ARG(y && gamma && beta && scale && shift && out, "uia_bn_add_relu_fwd: null tensor");
+    UIA_CHECK_ARG(eps > 0.f && momentum >= 0.f && momentum <= 1.f, "uia_bn_add_relu_fwd: eps must be > 0 and momentum in [0, 1]");
+    if (training) {
+        UIA_CHECK_ARG(ws && mean && invstd, "uia_bn_add_relu_fwd: training needs ws, mean and invstd");
+        UIA_CHECK_ARG((run_mean == nullptr) == (run_var == nullptr), "uia_bn_add_relu_fwd: running mean and variance come together");
+        const int S = slices_for(M);
+        if (dtype == UIA_BF16)
+            hipLaunchKernelGGL((reduce_kernel<bf16_t, RED_STATS>), dim3(S), dim3(256), 0, stream, M, C, (const bf16_t*)y, nullptr, nullptr, nullptr, nullptr, nullptr, ws);
+        else
+            hipLaunchKernelGGL((reduce_kernel<float, RED_STATS>), dim3(S), dim3(256), 0, stream, M, C, (const float*)y, nullptr, nullptr, nullptr, nullptr, nullptr, ws);
+        UIA_CHECK_LAUNCH();
+        hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + 255) / 256), dim3(256), 0, stream, M, C, S, ws, gamma, beta, eps, momentum, mean, invstd, scale, shift,
+                           run_mean, run_var, nbt);
+    } else {
+        UIA_CHECK_ARG(run_mean && run_var, "uia_bn_add_relu_fwd: eval mode needs the running buffers");
+        hipLaunchKernelGGL(bn_eval_coeff_kernel, dim3((C + 255) / 256), dim3(256), 0, stream, C, gamma, beta, run_mean, run_var, eps, scale, shift);
+    }
+    UIA_CHECK_LAUNCH();
+    const long n = M * C;
+    if (dtype == UIA_BF16)
+        hipLaunchKernelGGL(bn_add_relu_apply_kernel<bf16_t>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, n, C, (const bf16_t*)y, (const bf16_t*)r, scale, shift,
+                           (bf16_t*)out);
+    else
+        hipLaunchKernelGGL(bn_add_relu_apply_kernel<float>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, n, C, (const float*)y, (const float*)r, scale, shift,
+                           (float*)out);
+    UIA_CHECK_LAUNCH();
+    return 0;
+}
+
+int uia_bn_add_relu_bwd_launch(hipStream_t stream, int dtype, long M, int C, const void* y, const void* out, const void* dout, const float* mean,
+                               const float* invstd, const float* gamma, float* ws, float* dgamma, float* dbeta, void* dy, void* dr) {
+    BN_ARGS_OK("uia_bn_add_relu_bwd");
+    UIA_CHECK_ARG(y && out && dout && mean && invstd && gamma && ws && dgamma && dbeta && dy, "uia_bn_add_relu_bwd: null tensor");
+    const int S = slices_for(M);
+    if (dtype == UIA_BF16)
+        hipLaunchKernelGGL(reduce_add_relu_bwd_kernel<bf16_t>, dim3(S), dim3(256), 0, stream, M, C, (const bf16_t*)y, (const bf16_t*)out, (const bf16_t*)dout, mean, invstd, ws);
+    else
+        hipLaunchKernelGGL(reduce_add_relu_bwd_kernel<float>, dim3(S), dim3(256), 0, stream, M, C, (const float*)y, (const float*)out, (const float*)dout, mean, invstd, ws);
+    UIA_CHECK_LAUNCH();
+    hipLaunchKernelGGL(col_finalize_kernel, dim3((C + 255) / 256), dim3(256), 0, stream, C, S, ws, dbeta, dgamma);
+    UIA_CHECK_LAUNCH();
+    const long n = M * C;
+    if (dtype == UIA_BF16)
+        hipLaunchKernelGGL(bn_add_relu_bwd_apply_kernel<bf16_t>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, M, C, (const bf16_t*)y, (const bf16_t*)out,
+                           (const bf16_t*)dout, mean, invstd, gamma, dbeta, dgamma, (bf16_t*)dy, (bf16_t*)dr);
+    else
+        hipLaunchKernelGGL(bn_add_relu_bwd_apply_kernel<float>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, M, C, (const float*)y, (const float*)out,
+                           (const float*)dout, mean, invstd, gamma, dbeta, dgamma, (float*)dy, (float*)dr);
+    UIA_CHECK_LAUNCH();
+    return 0;
+}

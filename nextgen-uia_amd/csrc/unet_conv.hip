@@ -497,3 +497,323 @@ int uia_conv_wgrad_launch(hipStream_t stream, int dtype, int mode, int B, int H,
     }
     return 0;
 }
+
+// ================================================================ strided convolution (the ResNet baseline, src/third_party/resnet.py)
+// Conv2d(k, stride s, padding k/2, bias=False), k in {1, 3, 7}, s in {1, 2}, on x [B,H,W,C] -> y [B,Ho,Wo,N], Ho = (H − 1)/s + 1.
+// One kernel for the forward and the data gradient: both are D[m][n] = Σ_k Wr[n][k]·Src[m][k] over a destination pixel grid.
+//   forward        destination Ho×Wo, N channels; source x; pixel (y, x), tap (ky, kx) reads (s·y + ky − k/2, s·x + kx − k/2).  Wr [N][k²·C].
+//   data gradient  destination H×W, C channels; source dy on Ho×Wo; pixel (y, x) takes tap (ky, kx) only where y + k/2 − ky and x + k/2 − kx
+//                  are divisible by s and the quotient lies inside Ho×Wo.  Wr [C][k²·N] (column (ky·k + kx)·N + n, taps not flipped).
+//                  All k² taps run, the invalid ones as zeros (at s = 2 about three quarters of them).
+// The workgroup tile, the LDS layout and the K loop are conv_igemm_kernel<T, true>'s: tap decoded per 8-element chunk, last K step zero-filled.
+namespace {
+
+struct SGeo {
+    int dgrad;          // 0: forward, 1: data gradient
+    int B, Hd, Wd;      // destination pixel grid
+    int Hs, Ws;         // source pixel grid
+    int Cs, Nd;         // source / destination channels
+    int k, s;
+};
+
+__device__ __forceinline__ long strided_src_pixel(const SGeo& g, int b, int y, int x, int t) {
+    const int ky = t / g.k, kx = t - ky * g.k, h = g.k >> 1;
+    int yy, xx;
+    if (!g.dgrad) {
+        yy = g.s * y + ky - h;
+        xx = g.s * x + kx - h;
+    } else {
+        yy = y + h - ky;
+        xx = x + h - kx;
+        if (yy < 0 || xx < 0) return -1;
+        if (g.s == 2) {
+            if ((yy | xx) & 1) return -1;
+            yy >>= 1;
+            xx >>= 1;
+        }
+    }
+    if (yy < 0 || yy >= g.Hs || xx < 0 || xx >= g.Ws) return -1;
+    return ((long)b * g.Hs + yy) * g.Ws + xx;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void conv_strided_kernel(SGeo g, const T* __restrict__ src, const T* __restrict__ w, T* __restrict__ out) {
+    constexpr int R = Lds<T>::ROW;
+    __shared__ __attribute__((aligned(16))) T Ws[TN * R];
+    __shared__ __attribute__((aligned(16))) T Xs[TM * R];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long M = (long)g.B * g.Hd * g.Wd;
+    const long m0 = (long)blockIdx.x * TM;
+    const int n0 = blockIdx.y * TN;
+    const int K = g.k * g.k * g.Cs;
+
+    int pb[2], py[2], px[2];
+    bool pv[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const long m = m0 + (tid >> 2) + 64 * i;
+        pv[i] = m < M;
+        const long mm = pv[i] ? m : 0;
+        px[i] = (int)(mm % g.Wd);
+        py[i] = (int)((mm / g.Wd) % g.Hd);
+        pb[i] = (int)(mm / ((long)g.Wd * g.Hd));
+    }
+    const int kq = (tid & 3) * 8;
+    const int wn = n0 + (tid >> 2);
+    f32x4_t acc[4][2];
+#pragma unroll
+    for (int a = 0; a < 4; ++a)
+#pragma unroll
+        for (int b = 0; b < 2; ++b) acc[a][b] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+
+    for (int k0 = 0; k0 < K; k0 += KC) {
+        const bool kin = k0 + kq < K;
+        const int kk = kin ? k0 + kq : 0;
+        const int t = kk / g.Cs, cs = kk - t * g.Cs;
+        T v[2][8], wv[8];
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const long p = pv[i] && kin ? strided_src_pixel(g, pb[i], py[i], px[i], t) : -1;
+            if (p >= 0) load_chunk8(src + p * g.Cs + cs, v[i]);
+            else zero8(v[i]);
+        }
+        if (wn < g.Nd && kin) load_chunk8(w + (long)wn * K + k0 + kq, wv);
+        else zero8(wv);
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < 2; ++i) lds_put8(Xs + ((tid >> 2) + 64 * i) * R + kq, v[i]);
+        lds_put8(Ws + (tid >> 2) * R + kq, wv);
+        __syncthreads();
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+#pragma unroll
+            for (int b = 0; b < 2; ++b) acc[a][b] = mma_k32<T>(Ws + 16 * a * R, Xs + (32 * wave + 16 * b) * R, lane, acc[a][b]);
+    }
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+        const long m = m0 + 32 * wave + 16 * b + (lane & 15);
+        if (m >= M) continue;
+#pragma unroll
+        for (int a = 0; a < 4; ++a) {
+            const int n = n0 + 16 * a + 4 * (lane >> 4);
+            if (n < g.Nd) store4(out + m * g.Nd + n, acc[a][b]);
+        }
+    }
+}
+
+// direct form of the same contract: one thread per (destination pixel, destination channel); any channel counts, any alignment
+template <typename T>
+__global__ __launch_bounds__(256) void conv_strided_direct_kernel(SGeo g, const T* __restrict__ src, const T* __restrict__ w, T* __restrict__ out) {
+    const long M = (long)g.B * g.Hd * g.Wd;
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= M * g.Nd) return;
+    const long m = i / g.Nd;
+    const int n = (int)(i - m * g.Nd);
+    const int taps = g.k * g.k;
+    const int xx = (int)(m % g.Wd), yy = (int)((m / g.Wd) % g.Hd), bb = (int)(m / ((long)g.Wd * g.Hd));
+    const T* wr = w + (long)n * taps * g.Cs;
+    float s = 0.f;
+    for (int t = 0; t < taps; ++t) {
+        const long p = strided_src_pixel(g, bb, yy, xx, t);
+        if (p < 0) continue;
+        const T* a = src + p * g.Cs;
+        for (int c = 0; c < g.Cs; ++c) s = fmaf(to_f32(a[c]), to_f32(wr[t * g.Cs + c]), s);
+    }
+    out[i] = from_f32<T>(s);
+}
+
+// weight gradient: G[n][col] = Σ_m dy[m][n]·Q[m][col] over the Ho×Wo output pixels, Q the strided gather of x (col = tap·C + c)
+struct SWGeo {
+    int B, H, W, Ho, Wo;
+    int C, N, k, s;
+    int Cols;           // k²·C
+    long per;           // output pixels per split (multiple of 32)
+};
+
+template <typename T>
+__device__ __forceinline__ void strided_q_chunk(const SWGeo& g, const T* x, int b, int y, int xo, int col, T (&v)[8]) {
+    const int t = col / g.C, c = col - t * g.C;
+    const int ky = t / g.k, kx = t - ky * g.k;
+    const int yy = g.s * y + ky - (g.k >> 1), xx = g.s * xo + kx - (g.k >> 1);
+    if (yy < 0 || yy >= g.H || xx < 0 || xx >= g.W) { zero8(v); return; }
+    load_chunk8(x + (((long)b * g.H + yy) * g.W + xx) * g.C + c, v);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void conv_strided_wgrad_kernel(SWGeo g, const T* __restrict__ x, const T* __restrict__ dy, float* __restrict__ out) {
+    constexpr int R = Lds<T>::ROW;
+    __shared__ __attribute__((aligned(16))) T Qs[64 * R];
+    __shared__ __attribute__((aligned(16))) T Ps[64 * R];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long M = (long)g.B * g.Ho * g.Wo;
+    const int col0 = blockIdx.x * 64, r0 = blockIdx.y * 64;
+    const long mbeg = (long)blockIdx.z * g.per;
+    const long mend = mbeg + g.per < M ? mbeg + g.per : M;
+    const int lm = tid >> 3, lc = (tid & 7) * 8;
+    const int qc = col0 + lc, pr = r0 + lc;
+    f32x4_t acc[4];
+#pragma unroll
+    for (int a = 0; a < 4; ++a) acc[a] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    for (long mk = mbeg; mk < mend; mk += 32) {
+        const long m = mk + lm;
+        T qv[8], pvv[8];
+        if (m < mend) {
+            const int xo = (int)(m % g.Wo), y = (int)((m / g.Wo) % g.Ho), b = (int)(m / ((long)g.Wo * g.Ho));
+            if (qc < g.Cols) strided_q_chunk(g, x, b, y, xo, qc, qv); else zero8(qv);
+            if (pr < g.N) load_chunk8(dy + m * g.N + pr, pvv); else zero8(pvv);
+        } else {
+            zero8(qv);
+            zero8(pvv);
+        }
+        __syncthreads();
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            Qs[(lc + e) * R + lm] = qv[e];
+            Ps[(lc + e) * R + lm] = pvv[e];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int a = 0; a < 4; ++a) acc[a] = mma_k32<T>(Qs + 16 * a * R, Ps + 16 * wave * R, lane, acc[a]);
+    }
+    const int r = r0 + 16 * wave + (lane & 15);
+    if (r >= g.N) return;
+    float* o = out + (size_t)blockIdx.z * g.N * g.Cols + (size_t)r * g.Cols;
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+        const int c = col0 + 16 * a + 4 * (lane >> 4);
+        if (c < g.Cols) store4(o + c, acc[a]);
+    }
+}
+
+// direct weight gradient: 64 outputs × 4 pixel lanes per workgroup, the lanes added in lane order (as conv_wgrad_direct_kernel)
+template <typename T>
+__global__ __launch_bounds__(256) void conv_strided_wgrad_direct_kernel(SWGeo g, const T* __restrict__ x, const T* __restrict__ dy, float* __restrict__ out) {
+    __shared__ float part[4][64];
+    const int tid = threadIdx.x, j = tid & 63, lane4 = tid >> 6;
+    const long idx = (long)blockIdx.x * 64 + j;
+    const long total = (long)g.N * g.Cols;
+    const long M = (long)g.B * g.Ho * g.Wo;
+    const long mbeg = (long)blockIdx.y * g.per;
+    const long mend = mbeg + g.per < M ? mbeg + g.per : M;
+    float s = 0.f;
+    if (idx < total) {
+        const int r = (int)(idx / g.Cols), col = (int)(idx - (long)r * g.Cols);
+        const int t = col / g.C, c = col - t * g.C, ky = t / g.k, kx = t - ky * g.k, h = g.k >> 1;
+        const int HW = g.Ho * g.Wo;
+        for (int m = (int)mbeg + lane4; m < (int)mend; m += 4) {
+            const int b = m / HW, r2 = m - b * HW, y = r2 / g.Wo, xo = r2 - y * g.Wo;
+            const int yy = g.s * y + ky - h, xx = g.s * xo + kx - h;
+            if (yy < 0 || yy >= g.H || xx < 0 || xx >= g.W) continue;
+            s = fmaf(to_f32(x[(((long)b * g.H + yy) * g.W + xx) * g.C + c]), to_f32(dy[(long)m * g.N + r]), s);
+        }
+    }
+    part[lane4][j] = s;
+    __syncthreads();
+    if (lane4 == 0 && idx < total) out[(size_t)blockIdx.y * total + idx] = ((part[0][j] + part[1][j]) + part[2][j]) + part[3][j];
+}
+
+bool strided_ks_ok(int k, int s) { return (k == 1 || k == 3 || k == 7) && (s == 1 || s == 2); }
+
+}  // namespace
+
+// 1: the matrix-core kernel (for 16-byte-aligned operands), 0: the direct kernel.  dgrad is 0 (forward) or 1 (data gradient); the rule is the same.
+int uia_conv_strided_form(int dgrad, int C, int N, int k, int s) {
+    if ((dgrad != 0 && dgrad != 1) || !strided_ks_ok(k, s) || C <= 0 || N <= 0) return 0;
+    return C % 8 == 0 && N % 8 == 0;
+}
+int uia_conv_strided_wgrad_form(int C, int N, int k, int s) {
+    if (!strided_ks_ok(k, s) || C <= 0 || N <= 0) return 0;
+    return C % 8 == 0 && N % 8 == 0;
+}
+
+#define STRIDED_ARGS_OK(fn)                                                                                                                  \
+    UIA_CHECK_ARG(dtype == UIA_F32 || dtype == UIA_BF16, fn ": dtype must be UIA_F32 or UIA_BF16");                                        \
+    UIA_CHECK_ARG(k == 1 || k == 3 || k == 7, fn ": kernel size k=%d is not 1, 3 or 7", k);                                                \
+    UIA_CHECK_ARG(s == 1 || s == 2, fn ": stride s=%d is not 1 or 2", s);                                                                  \
+    UIA_CHECK_ARG(B > 0 && H > 0 && W > 0 && C > 0 && N > 0, fn ": B=%d H=%d W=%d C=%d N=%d must be positive", B, H, W, C, N);             \
+    UIA_CHECK_ARG((long)B * H * W * C * k * k < (1l << 40) && (long)(C > N ? C : N) * k * k < (1 << 20) && (long)B * H * W < (1l << 31), \
+                  fn ": shape too large")
+
+int uia_conv_strided_launch(hipStream_t stream, int dtype, int dgrad, int B, int H, int W, int C, int k, int s, const void* x, int N, const void* w,
+                            void* y) {
+    STRIDED_ARGS_OK("uia_conv_strided");
+    UIA_CHECK_ARG(dgrad == 0 || dgrad == 1, "uia_conv_strided: dgrad must be 0 (forward) or 1 (data gradient), got %d", dgrad);
+    UIA_CHECK_ARG(x && w && y, "uia_conv_strided: null tensor");
+    const int Ho = (H - 1) / s + 1, Wo = (W - 1) / s + 1;
+    SGeo g = dgrad ? SGeo{1, B, H, W, Ho, Wo, N, C, k, s} : SGeo{0, B, Ho, Wo, H, W, C, N, k, s};
+    const long M = (long)g.B * g.Hd * g.Wd;
+    const size_t es = dtype == UIA_BF16 ? 2 : 4;
+    const bool mfma = uia_conv_strided_form(dgrad, C, N, k, s) && aligned16(x) && aligned16(w) && ((uintptr_t)y % (4 * es)) == 0;
+    if (mfma) {
+        dim3 grid((unsigned)((M + TM - 1) / TM), (unsigned)((g.Nd + TN - 1) / TN));
+        if (dtype == UIA_BF16)
+            hipLaunchKernelGGL(conv_strided_kernel<bf16_t>, grid, dim3(256), 0, stream, g, (const bf16_t*)x, (const bf16_t*)w, (bf16_t*)y);
+        else
+            hipLaunchKernelGGL(conv_strided_kernel<float>, grid, dim3(256), 0, stream, g, (const float*)x, (const float*)w, (float*)y);
+    } else {
+        const long n = M * g.Nd;
+        dim3 grid((unsigned)((n + 255) / 256));
+        if (dtype == UIA_BF16)
+            hipLaunchKernelGGL(conv_strided_direct_kernel<bf16_t>, grid, dim3(256), 0, stream, g, (const bf16_t*)x, (const bf16_t*)w, (bf16_t*)y);
+        else
+            hipLaunchKernelGGL(conv_strided_direct_kernel<float>, grid, dim3(256), 0, stream, g, (const float*)x, (const float*)w, (float*)y);
+    }
+    UIA_CHECK_LAUNCH();
+    return 0;
+}
+
+// the rule of uia_conv_wgrad_splits on the Ho×Wo pixels, the narrow-channel cap included
+int uia_conv_strided_wgrad_splits(int B, int H, int W, int C, int k, int s, int N) {
+    if (!strided_ks_ok(k, s) || B <= 0 || H <= 0 || W <= 0 || C <= 0 || N <= 0) return 1;
+    const long M = (long)B * ((H - 1) / s + 1) * ((W - 1) / s + 1);
+    const int Cols = k * k * C;
+    long S;
+    if (uia_conv_strided_wgrad_form(C, N, k, s)) {
+        const long tiles = (long)((Cols + 63) / 64) * ((N + 63) / 64);
+        const bool narrow = C % KC != 0;
+        const long cap = narrow ? UIA_WGRAD_MAX_NARROW_SPLITS : UIA_WGRAD_MAX_SPLITS;
+        S = ((narrow ? 8 : 2) * uia_num_cus() + tiles - 1) / tiles;
+        S = S < 1 ? 1 : (S > cap ? cap : S);
+    } else {
+        const long groups = ((long)N * Cols + 63) / 64;
+        S = (8 * uia_num_cus() + groups - 1) / groups;
+        S = S < 1 ? 1 : (S > UIA_WGRAD_MAX_DIRECT_SPLITS ? UIA_WGRAD_MAX_DIRECT_SPLITS : S);
+    }
+    const long chunks = (M + 31) / 32;
+    if (S > chunks) S = chunks;
+    return (int)S;
+}
+
+int uia_conv_strided_wgrad_launch(hipStream_t stream, int dtype, int B, int H, int W, int C, int k, int s, const void* x, int N, const void* dy,
+                                  float* ws, float* dw) {
+    STRIDED_ARGS_OK("uia_conv_strided_wgrad");
+    UIA_CHECK_ARG(x && dy && dw, "uia_conv_strided_wgrad: null tensor");
+    const int S = uia_conv_strided_wgrad_splits(B, H, W, C, k, s, N);
+    UIA_CHECK_ARG(S == 1 || ws, "uia_conv_strided_wgrad: %d splits need scratch (uia_conv_strided_wgrad_splits · N · k²·C floats)", S);
+    SWGeo g{B, H, W, (H - 1) / s + 1, (W - 1) / s + 1, C, N, k, s, k * k * C, 0};
+    const long M = (long)B * g.Ho * g.Wo;
+    g.per = ((M + S - 1) / S + 31) / 32 * 32;
+    float* dst = S == 1 ? dw : ws;
+    const bool mfma = uia_conv_strided_wgrad_form(C, N, k, s) && aligned16(x) && aligned16(dy) && aligned16(dst);
+    if (mfma) {
+        dim3 grid((unsigned)((g.Cols + 63) / 64), (unsigned)((N + 63) / 64), (unsigned)S);
+        if (dtype == UIA_BF16)
+            hipLaunchKernelGGL(conv_strided_wgrad_kernel<bf16_t>, grid, dim3(256), 0, stream, g, (const bf16_t*)x, (const bf16_t*)dy, dst);
+        else
+            hipLaunchKernelGGL(conv_strided_wgrad_kernel<float>, grid, dim3(256), 0, stream, g, (const float*)x, (const float*)dy, dst);
+    } else {
+        const long total = (long)N * g.Cols;
+        dim3 grid((unsigned)((total + 63) / 64), (unsigned)S);
+        if (dtype == UIA_BF16)
+            hipLaunchKernelGGL(conv_strided_wgrad_direct_kernel<bf16_t>, grid, dim3(256), 0, stream, g, (const bf16_t*)x, (const bf16_t*)dy, dst);
+        else
+            hipLaunchKernelGGL(conv_strided_wgrad_direct_kernel<float>, grid, dim3(256), 0, stream, g, (const float*)x, (const float*)dy, dst);
+    }
+    UIA_CHECK_LAUNCH();
+    if (S > 1) {
+        const long n = (long)N * g.Cols;
+        hipLaunchKernelGGL(split_sum_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, S, n, ws, dw);
+        UIA_CHECK_LAUNCH();
+    }
+    return 0;
+}

@@ -110,6 +110,19 @@ PROTOTYPES = {
     "uia_bn_act_bwd": (C.c_int, [vp, C.c_int, i64, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, f32, f32, C.c_uint64, vp]),
     "uia_maxpool2_fwd": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
     "uia_maxpool2_bwd": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
+    "uia_conv_strided": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp]),
+    "uia_conv_strided_wgrad_splits": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "uia_conv_strided_form": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "uia_conv_strided_wgrad_form": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "uia_conv_strided_wgrad": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int, vp, vp, vp]),
+    "uia_maxpool3s2_fwd": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
+    "uia_maxpool3s2_bwd": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp]),
+    "uia_bn_add_relu_fwd": (C.c_int, [vp, C.c_int, C.c_int, i64, C.c_int, vp, vp, vp, vp, vp, vp, vp, f32, f32, vp, vp, vp, vp, vp, vp]),
+    "uia_bn_add_relu_bwd": (C.c_int, [vp, C.c_int, i64, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "uia_avgpool_fwd": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
+    "uia_avgpool_bwd": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
+    "uia_nchw_to_nhwc": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]),
+    "uia_add2": (C.c_int, [vp, C.c_int, i64, vp, vp, vp]),
     "uia_bn_fwd": (C.c_int, [vp, C.c_int, C.c_int, i64, C.c_int, vp, vp, vp, vp, vp, vp, f32, f32, vp, vp, vp, vp, vp, C.c_int, vp]),
     "uia_bn_relu_bwd": (C.c_int, [vp, C.c_int, i64, C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "uia_colsum_ordered": (C.c_int, [vp, C.c_int, i64, C.c_int, vp, vp, vp]),

@@ -2035,3 +2035,148 @@ class ResizeAAFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         return ops.resize_aa_bwd(dy.contiguous().float(), ctx.hw, ctx.dt), None
+
+
+# ---------------------------------------------------------------- ResNet baseline (src/third_party/resnet.py; NHWC activations in the compute dtype)
+def strided_rows(w, dt, cin=None):
+    """Conv2d weight [Cout, Cw, k, k] -> uia_conv_strided's forward rows [Cout, k·k·cin] (column (ky·k + kx)·cin + c).  cin > Cw (the stem:
+    3 channels in 8) zero-fills the pad channels on the device (uia_nchw_to_nhwc: the weight is an NCHW batch of Cout k×k images)."""
+    n, cw, k, _ = w.shape
+    if cin is not None and cin != cw:
+        return ops.nchw_to_nhwc(w.detach().float().contiguous(), cin, cw, dt).view(n, k * k * cin)
+    return w.detach().permute(0, 2, 3, 1).reshape(n, -1).to(dt).contiguous()
+
+
+def strided_dgrad_rows(w, dt):
+    """The data gradient's rows [Cin, k·k·Cout] (column (ky·k + kx)·Cout + o; the taps are not flipped, the kernel gathers by them)."""
+    return w.detach().permute(1, 2, 3, 0).reshape(w.shape[1], -1).to(dt).contiguous()
+
+
+def _res_conv_bn_forward(ctx, mode, x, r, w, gamma, beta, running_mean, running_var, nbt, training, momentum, eps, stride):
+    dt = x.dtype
+    n, cw, k, _ = w.shape
+    cin = x.shape[3]
+    if cw > cin or (cw != cin and cin != 8):
+        raise UiaError(f"conv: weight takes {cw} channels, the activation has {cin}")
+    y = ops.conv_strided(x, strided_rows(w, dt, cin), n, k, stride)
+    g, b = gamma.detach(), beta.detach()
+    if mode == "relu":
+        out, mean, invstd, scale, shift = ops.bn_fwd(y, g, b, running_mean, running_var, nbt, training, momentum, eps, relu=True)
+    elif mode == "none":
+        out, mean, invstd, scale, shift = ops.bn_act_fwd(y, g, b, running_mean, running_var, nbt, training, momentum, eps, slope=1.0, drop_p=0.0)
+    else:
+        out, mean, invstd, scale, shift = ops.bn_add_relu_fwd(y, r, g, b, running_mean, running_var, nbt, training, momentum, eps)
+    if training:
+        ctx.save_for_backward(x, w, y, gamma, mean, invstd, scale, shift, out if mode == "add_relu" else None)
+    ctx.training, ctx.mode, ctx.stride = training, mode, int(stride)
+    return out
+
+
+def _res_conv_bn_backward(ctx, dout, x_needs_grad):
+    """-> (dx, dr, dw, dgamma, dbeta)"""
+    if not ctx.training:
+        raise UiaError("ResNet conv + BatchNorm: eval-mode BatchNorm has no backward here (the baseline trains in train mode)")
+    x, w, y, gamma, mean, invstd, scale, shift, out = ctx.saved_tensors
+    dout = dout.contiguous()
+    g = gamma.detach()
+    dr = None
+    if ctx.mode == "relu":
+        dy, dgamma, dbeta = ops.bn_relu_bwd(y, dout, scale, shift, mean, invstd, g)
+    elif ctx.mode == "none":
+        dy, dgamma, dbeta = ops.bn_act_bwd(y, dout, scale, shift, mean, invstd, g, slope=1.0, drop_p=0.0)
+    else:
+        dy, dr, dgamma, dbeta = ops.bn_add_relu_bwd(y, out, dout, mean, invstd, g)
+    n, cw, k, _ = w.shape
+    cin = x.shape[3]
+    dw = ops.conv_strided_wgrad(x, dy, k, ctx.stride).reshape(n, k, k, cin)[..., :cw].permute(0, 3, 1, 2).contiguous()
+    dx = None
+    if x_needs_grad:
+        if cw != cin:
+            raise UiaError("the packed stem has no data gradient (the images need none)")
+        dx = ops.conv_strided_dgrad(dy, strided_dgrad_rows(w, dy.dtype), (x.shape[1], x.shape[2]), cin, k, ctx.stride)
+    return dx, dr, dw, dgamma, dbeta
+
+
+class ConvBNReLUFn(torch.autograd.Function):
+    """ReLU(BatchNorm2d(Conv2d(k, stride, padding k//2, bias=False)(x))) on NHWC x; w [Cout, Cin, k, k] as nn.Conv2d keeps it, k in (1, 3, 7),
+    stride in (1, 2).  An x of 8 channels under a weight of fewer is the packed stem: the weight's pad channels are zeros and their gradient
+    columns are dropped.  training: batch statistics, running buffers updated on the device; eval: the running statistics (no backward)."""
+
+    @staticmethod
+    def forward(ctx, x, w, gamma, beta, running_mean, running_var, nbt, training, momentum, eps, stride):
+        return _res_conv_bn_forward(ctx, "relu", x, None, w, gamma, beta, running_mean, running_var, nbt, training, momentum, eps, stride)
+
+    @staticmethod
+    def backward(ctx, dout):
+        dx, _, dw, dgamma, dbeta = _res_conv_bn_backward(ctx, dout, ctx.needs_input_grad[0])
+        return dx, dw, dgamma, dbeta, None, None, None, None, None, None, None
+
+
+class ConvBNFn(torch.autograd.Function):
+    """BatchNorm2d(Conv2d(...)(x)) with no activation: the downsample branch of a BasicBlock (uia_bn_act_* with slope 1, no dropout)."""
+
+    @staticmethod
+    def forward(ctx, x, w, gamma, beta, running_mean, running_var, nbt, training, momentum, eps, stride):
+        return _res_conv_bn_forward(ctx, "none", x, None, w, gamma, beta, running_mean, running_var, nbt, training, momentum, eps, stride)
+
+    @staticmethod
+    def backward(ctx, dout):
+        dx, _, dw, dgamma, dbeta = _res_conv_bn_backward(ctx, dout, ctx.needs_input_grad[0])
+        return dx, dw, dgamma, dbeta, None, None, None, None, None, None, None
+
+
+class ConvBNAddReLUFn(torch.autograd.Function):
+    """ReLU(BatchNorm2d(Conv2d(...)(x)) + r): the tail of a BasicBlock; r [B, Ho, Wo, Cout] is the identity or the downsample branch."""
+
+    @staticmethod
+    def forward(ctx, x, r, w, gamma, beta, running_mean, running_var, nbt, training, momentum, eps, stride):
+        if tuple(r.shape) != (x.shape[0], *ops.strided_out_hw(x.shape[1], x.shape[2], int(stride)), w.shape[0]):
+            raise UiaError(f"ConvBNAddReLUFn: residual {tuple(r.shape)} does not match the conv's output")
+        return _res_conv_bn_forward(ctx, "add_relu", x, r.contiguous(), w, gamma, beta, running_mean, running_var, nbt, training, momentum, eps, stride)
+
+    @staticmethod
+    def backward(ctx, dout):
+        dx, dr, dw, dgamma, dbeta = _res_conv_bn_backward(ctx, dout, ctx.needs_input_grad[0])
+        return dx, dr, dw, dgamma, dbeta, None, None, None, None, None, None, None
+
+
+class ResidualForkFn(torch.autograd.Function):
+    """x -> (x, x) for the two branches of a residual block; the backward adds the two gradients with uia_add2 (one fp32 sum per element,
+    rounded once) instead of autograd's accumulation."""
+
+    @staticmethod
+    def forward(ctx, x):
+        return x.view_as(x), x.view_as(x)
+
+    @staticmethod
+    def backward(ctx, g1, g2):
+        if g1 is None or g2 is None:
+            return g1 if g2 is None else g2
+        return ops.add2(g1.contiguous(), g2.contiguous())
+
+
+class MaxPool3s2Fn(torch.autograd.Function):
+    """nn.MaxPool2d(3, 2, 1) on NHWC; the backward recomputes the argmax from the saved input."""
+
+    @staticmethod
+    def forward(ctx, x):
+        ctx.save_for_backward(x)
+        return ops.maxpool3s2(x)
+
+    @staticmethod
+    def backward(ctx, dy):
+        (x,) = ctx.saved_tensors
+        return ops.maxpool3s2_bwd(x, dy.contiguous())
+
+
+class GlobalAvgPoolFn(torch.autograd.Function):
+    """nn.AdaptiveAvgPool2d(1) + flatten on NHWC x [B,H,W,C] -> fp32 [B,C]."""
+
+    @staticmethod
+    def forward(ctx, x):
+        ctx.hw, ctx.dt = (x.shape[1], x.shape[2]), x.dtype
+        return ops.avgpool(x)
+
+    @staticmethod
+    def backward(ctx, dout):
+        return ops.avgpool_bwd(dout.contiguous().float(), ctx.hw, ctx.dt)

@@ -1884,3 +1884,180 @@ def resize_aa_bwd(dout, in_hw, dtype):
     dx = torch.empty(B, Hi, Wi, C, device=dout.device, dtype=dtype)
     check(lib().uia_resize_aa(_stream(), _code(dtype), 1, B, C, Hi, Wi, Ho, Wo, None, _p(tmp), None, _p(dout), _p(dx)), "uia_resize_aa")
     return dx
+
+
+# ---------------------------------------------------------------- ResNet baseline (csrc/unet_conv.hip, unet_pool.hip, unet_bn.hip)
+def _strided_ks(name, k, s):
+    k, s = int(k), int(s)
+    if k not in (1, 3, 7) or s not in (1, 2):
+        raise UiaError(f"{name}: kernel size {k} / stride {s} not built (k in 1, 3, 7; s in 1, 2)")
+    return k, s
+
+
+def strided_out_hw(h, w, s):
+    """The output grid of Conv2d(k, stride s, padding k//2) for odd k, and of MaxPool2d(3, 2, 1) at s = 2."""
+    return (h - 1) // s + 1, (w - 1) // s + 1
+
+
+def conv_strided(x, w, n, k, s):
+    """uia_conv_strided forward: Conv2d(k, stride s, padding k//2, bias=False) of NHWC x [B,H,W,C] with w [n, k·k·C] -> [B,Ho,Wo,n]."""
+    k, s = _strided_ks("conv_strided", k, s)
+    _nhwc(x, "conv_strided x")
+    B, H, W, C = x.shape
+    if w.dtype != x.dtype or not w.is_contiguous() or tuple(w.shape) != (n, k * k * C):
+        raise UiaError(f"conv_strided: w must be contiguous {x.dtype} [{n}, {k * k * C}], got {w.dtype} {tuple(w.shape)}")
+    Ho, Wo = strided_out_hw(H, W, s)
+    y = torch.empty(B, Ho, Wo, n, device=x.device, dtype=x.dtype)
+    check(lib().uia_conv_strided(_stream(), _code(x.dtype), 0, B, H, W, C, k, s, _p(x), n, _p(w), _p(y)), "uia_conv_strided")
+    return y
+
+
+def conv_strided_dgrad(dy, w, in_hw, c, k, s):
+    """uia_conv_strided data gradient: dy [B,Ho,Wo,n], w [c, k·k·n] (column (ky·k + kx)·n + o) -> dx [B,H,W,c] for the conv's input grid in_hw."""
+    k, s = _strided_ks("conv_strided_dgrad", k, s)
+    _nhwc(dy, "conv_strided_dgrad dy")
+    B, Ho, Wo, n = dy.shape
+    H, W = in_hw
+    if (Ho, Wo) != strided_out_hw(H, W, s):
+        raise UiaError(f"conv_strided_dgrad: dy grid {Ho}x{Wo} is not the stride-{s} output of {H}x{W}")
+    if w.dtype != dy.dtype or not w.is_contiguous() or tuple(w.shape) != (c, k * k * n):
+        raise UiaError(f"conv_strided_dgrad: w must be contiguous {dy.dtype} [{c}, {k * k * n}], got {w.dtype} {tuple(w.shape)}")
+    dx = torch.empty(B, H, W, c, device=dy.device, dtype=dy.dtype)
+    check(lib().uia_conv_strided(_stream(), _code(dy.dtype), 1, B, H, W, c, k, s, _p(dy), n, _p(w), _p(dx)), "uia_conv_strided")
+    return dx
+
+
+def conv_strided_wgrad(x, dy, k, s):
+    """uia_conv_strided_wgrad -> fp32 dW [n, k·k·C] from x [B,H,W,C] and dy [B,Ho,Wo,n]."""
+    k, s = _strided_ks("conv_strided_wgrad", k, s)
+    _nhwc(x, "conv_strided_wgrad x")
+    _nhwc(dy, "conv_strided_wgrad dy", x.dtype)
+    B, H, W, C = x.shape
+    n = dy.shape[3]
+    if tuple(dy.shape[:3]) != (B, *strided_out_hw(H, W, s)):
+        raise UiaError(f"conv_strided_wgrad: dy {tuple(dy.shape)}, expected {(B, *strided_out_hw(H, W, s), n)}")
+    cols = k * k * C
+    S = lib().uia_conv_strided_wgrad_splits(B, H, W, C, k, s, n)
+    ws = torch.empty(S * n * cols, device=x.device, dtype=torch.float32) if S > 1 else None
+    dw = torch.empty(n, cols, device=x.device, dtype=torch.float32)
+    check(lib().uia_conv_strided_wgrad(_stream(), _code(x.dtype), B, H, W, C, k, s, _p(x), n, _p(dy), _p(ws), _p(dw)), "uia_conv_strided_wgrad")
+    return dw
+
+
+def conv_strided_form(dgrad, c, n, k, s):
+    """1 when uia_conv_strided takes the matrix-core kernel for this shape (16-byte-aligned operands), 0 for the direct kernel.  No GPU needed."""
+    return int(lib().uia_conv_strided_form(int(dgrad), int(c), int(n), int(k), int(s)))
+
+
+def conv_strided_wgrad_form(c, n, k, s):
+    """1 when uia_conv_strided_wgrad takes the matrix-core kernel for this shape (16-byte-aligned operands), 0 for the direct kernel.  No GPU needed."""
+    return int(lib().uia_conv_strided_wgrad_form(int(c), int(n), int(k), int(s)))
+
+
+def maxpool3s2(x):
+    """nn.MaxPool2d(3, 2, 1) on NHWC x [B,H,W,C] -> [B,(H-1)//2+1,(W-1)//2+1,C] (uia_maxpool3s2_fwd); the padding is -inf."""
+    _nhwc(x, "maxpool3s2")
+    B, H, W, C = x.shape
+    y = torch.empty(B, *strided_out_hw(H, W, 2), C, device=x.device, dtype=x.dtype)
+    check(lib().uia_maxpool3s2_fwd(_stream(), _code(x.dtype), B, H, W, C, _p(x), _p(y)), "uia_maxpool3s2_fwd")
+    return y
+
+
+def maxpool3s2_bwd(x, dy):
+    """Backward of maxpool3s2 (uia_maxpool3s2_bwd): the argmax is recomputed from x; every element of dx [B,H,W,C] is written."""
+    _nhwc(x, "maxpool3s2_bwd x")
+    _nhwc(dy, "maxpool3s2_bwd dy", x.dtype)
+    B, H, W, C = x.shape
+    want = (B, *strided_out_hw(H, W, 2), C)
+    if tuple(dy.shape) != want:
+        raise UiaError(f"maxpool3s2_bwd: dy {tuple(dy.shape)}, expected {want}")
+    dx = torch.empty_like(x)
+    check(lib().uia_maxpool3s2_bwd(_stream(), _code(x.dtype), B, H, W, C, _p(x), _p(dy), _p(dx)), "uia_maxpool3s2_bwd")
+    return dx
+
+
+def bn_add_relu_fwd(y, r, gamma, beta, running_mean, running_var, num_batches_tracked, training, momentum=0.1, eps=1e-5):
+    """relu(BatchNorm2d(y) + r) on NHWC y, r (uia_bn_add_relu_fwd; r may be None).  Returns (out, mean, invstd, scale, shift) as bn_fwd does."""
+    _nhwc(y, "bn_add_relu_fwd y")
+    if r is not None:
+        _nhwc(r, "bn_add_relu_fwd r", y.dtype)
+        if r.shape != y.shape:
+            raise UiaError("bn_add_relu_fwd: r and y differ in shape")
+    C = y.shape[3]
+    M = y.numel() // C
+    for t, nm in ((gamma, "gamma"), (beta, "beta"), (running_mean, "running_mean"), (running_var, "running_var")):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != C):
+            raise UiaError(f"bn_add_relu_fwd: {nm} must be contiguous fp32 [{C}]")
+    if num_batches_tracked is not None and num_batches_tracked.dtype != torch.int64:
+        raise UiaError("bn_add_relu_fwd: num_batches_tracked must be int64")
+    f = lambda: torch.empty(C, device=y.device, dtype=torch.float32)   # noqa: E731
+    scale, shift = f(), f()
+    mean, invstd, ws = (f(), f(), torch.empty(BN_SLICES * C * 3, device=y.device, dtype=torch.float32)) if training else (None, None, None)
+    out = torch.empty_like(y)
+    check(lib().uia_bn_add_relu_fwd(_stream(), _code(y.dtype), int(bool(training)), M, C, _p(y), _p(r), _p(gamma), _p(beta), _p(running_mean),
+                                    _p(running_var), _p(num_batches_tracked), float(momentum), float(eps), _p(ws), _p(mean), _p(invstd), _p(scale),
+                                    _p(shift), _p(out)), "uia_bn_add_relu_fwd")
+    return out, mean, invstd, scale, shift
+
+
+def bn_add_relu_bwd(y, out, dout, mean, invstd, gamma, want_dr=True):
+    """Backward of train-mode bn_add_relu_fwd (uia_bn_add_relu_bwd): returns (dy, dr, dgamma, dbeta); dr is None without want_dr."""
+    _nhwc(y, "bn_add_relu_bwd y")
+    _nhwc(out, "bn_add_relu_bwd out", y.dtype)
+    _nhwc(dout, "bn_add_relu_bwd dout", y.dtype)
+    if dout.shape != y.shape or out.shape != y.shape:
+        raise UiaError("bn_add_relu_bwd: y, out and dout differ in shape")
+    C = y.shape[3]
+    for t, nm in ((mean, "mean"), (invstd, "invstd"), (gamma, "gamma")):
+        if t is None or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != C:
+            raise UiaError(f"bn_add_relu_bwd: {nm} must be contiguous fp32 [{C}]")
+    M = y.numel() // C
+    ws = torch.empty(BN_SLICES * C * 3, device=y.device, dtype=torch.float32)
+    dgamma = torch.empty(C, device=y.device, dtype=torch.float32)
+    dbeta = torch.empty(C, device=y.device, dtype=torch.float32)
+    dy = torch.empty_like(y)
+    dr = torch.empty_like(y) if want_dr else None
+    check(lib().uia_bn_add_relu_bwd(_stream(), _code(y.dtype), M, C, _p(y), _p(out), _p(dout), _p(mean), _p(invstd), _p(gamma), _p(ws), _p(dgamma),
+                                    _p(dbeta), _p(dy), _p(dr)), "uia_bn_add_relu_bwd")
+    return dy, dr, dgamma, dbeta
+
+
+def avgpool(x):
+    """Global average pool of NHWC x [B,H,W,C] -> fp32 [B,C] (uia_avgpool_fwd)."""
+    _nhwc(x, "avgpool")
+    B, H, W, C = x.shape
+    out = torch.empty(B, C, device=x.device, dtype=torch.float32)
+    check(lib().uia_avgpool_fwd(_stream(), _code(x.dtype), B, H, W, C, _p(x), _p(out)), "uia_avgpool_fwd")
+    return out
+
+
+def avgpool_bwd(dout, hw, dtype):
+    """Backward of avgpool: fp32 dout [B,C] -> dx [B,H,W,C] in dtype, dout/(H·W) at every pixel (uia_avgpool_bwd)."""
+    if dout.dim() != 2 or dout.dtype != torch.float32 or not dout.is_contiguous():
+        raise UiaError("avgpool_bwd: dout must be contiguous fp32 [B, C]")
+    B, C = dout.shape
+    H, W = hw
+    dx = torch.empty(B, H, W, C, device=dout.device, dtype=dtype)
+    check(lib().uia_avgpool_bwd(_stream(), _code(dtype), B, H, W, C, _p(dout), _p(dx)), "uia_avgpool_bwd")
+    return dx
+
+
+def nchw_to_nhwc(x, cout, rep, dtype):
+    """uia_nchw_to_nhwc: fp32 NCHW x [B,Cin,H,W] -> NHWC [B,H,W,cout] of dtype; channels c < rep filled (a one-channel x repeated), the rest zero."""
+    if x.dim() != 4 or x.dtype != torch.float32 or not x.is_contiguous():
+        raise UiaError("nchw_to_nhwc: x must be contiguous fp32 [B, C, H, W]")
+    B, Cin, H, W = x.shape
+    if not (0 <= rep <= cout and (rep <= Cin or Cin == 1)):
+        raise UiaError(f"nchw_to_nhwc: {rep} filled channels from {Cin} sources into {cout}")
+    out = torch.empty(B, H, W, cout, device=x.device, dtype=dtype)
+    check(lib().uia_nchw_to_nhwc(_stream(), _code(dtype), B, Cin, H, W, int(cout), int(rep), _p(x), _p(out)), "uia_nchw_to_nhwc")
+    return out
+
+
+def add2(a, b):
+    """a + b element-wise (uia_add2): the sum of a residual block's two input gradients."""
+    if a.shape != b.shape or a.dtype != b.dtype or not a.is_contiguous() or not b.is_contiguous():
+        raise UiaError("add2: two contiguous tensors of one shape and dtype are required")
+    out = torch.empty_like(a)
+    check(lib().uia_add2(_stream(), _code(a.dtype), a.numel(), _p(a), _p(b), _p(out)), "uia_add2")
+    return out
