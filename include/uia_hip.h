@@ -230,6 +230,13 @@ int uia_attn_bwd_cfg(void* stream, int dtype, const uia_attn_desc* d, int cfg);
  * Replaces the MemEffAttention of the DINOv2 tower (third_party/dino/vision_transformer.py [third-party], 1370 tokens at 518 px). */
 int uia_attn_fwd_long(void* stream, int dtype, const uia_attn_desc* d);
 
+/* uia_attn_bwd for a dout that is zero outside token 0 of every sequence (the CLS pool of a contrastive head): `dout` holds the B non-zero rows
+ * only, row b at dout[b·lddo + h·64 + d], and q, out and lse are read at token 0.  With P_j = exp(scale·q_0·k_j − lse_0) and δ = dout·out_0:
+ * dv_j = P_j·dout, dk_j = P_j(dout·v_j − δ)·scale·q_0, dq_0 = Σ_j P_j(dout·v_j − δ)·scale·k_j and dq_l = 0 for l > 0.  EVERY element of dq, dk and dv
+ * is written (the zero rows too), row-major or K-blocked (dqkv_kb_rows) as uia_attn_bwd writes them; out row-major or K-blocked (out_kb_rows).
+ * bf16 and fp32, head dim 64, L <= 288, mask kind none only; every pointer 16-byte aligned, every leading dimension a whole number of 16-byte units. */
+int uia_attn_bwd_cls(void* stream, int dtype, const uia_attn_desc* d);
+
 /* ---------------------------------------------------------------------------------------------
  * LayerNorm over fp32 rows (model.py:163-169; timm / HF LayerNorm [third-party]).
  * x rows may be strided by ldx (elements); y / dy are compact [M,D].  Backward is for FROZEN
@@ -258,6 +265,12 @@ int uia_layernorm_bwd(void* stream, int dtype, int M, int D, int64_t ldx, const 
 int uia_layernorm_bwd3(void* stream, int dtype, int M, int D, int64_t ldx, const void* dy, const float* x, const void* x_hi, const int8_t* x_lo, int64_t x_kb_rows,
                        const float* gamma, float eps, const float* dres, const void* dres_hi, const int8_t* dres_lo, int64_t dres_kb_rows, float* dx32, void* dxT,
                        int8_t* dx_lo);
+/* The same backward with a PERIODIC residual gradient: rows r with r % period == 0 take dres_rows[r / period] (compact fp32 [ceil(M / period), D]), every
+ * other row has none — the gradient of a block's residual stream when only token 0 of every `period` tokens carries one.  Bit-identical to
+ * uia_layernorm_bwd3 on dres_rows zero-padded to [M, D].  Compact rows (ldx == D).  Forms: bf16 with a three-byte result (dx_lo != NULL; x fp32 or
+ * three-byte as above) and fp32 (dx32 and / or dxT, x fp32). */
+int uia_layernorm_bwd_periodic(void* stream, int dtype, int M, int D, const void* dy, const float* x, const void* x_hi, const int8_t* x_lo, int64_t x_kb_rows,
+                               const float* gamma, float eps, const float* dres_rows, int period, float* dx32, void* dxT, int8_t* dx_lo);
 
 /* ---------------------------------------------------------------------------------------------
  * Mona adapter, all four variants (src/adapters/mona.py:75-487; equations SURVEY.md Appendix E.1).
@@ -316,6 +329,13 @@ int uia_mona_pre_bwd_du3(void* stream, int dtype, int M, int D, const void* dt, 
 size_t uia_mona_pre_bwd_workspace_bytes(int M, int D);
 int uia_mona_spatial_fwd(void* stream, int dtype, const uia_mona_spatial_desc* d);
 int uia_mona_spatial_bwd(void* stream, int dtype, const uia_mona_spatial_desc* d);
+/* The CLS token's share of uia_mona_spatial_bwd alone (the token bypasses the spatial operator, mona.py:132,139), for a gradient that is zero on
+ * every other token: dt[b, c] = dd[b, c] · keep(b·ntok·64 + c) · gelu'(t[b·ldt + c]) with compact dd / dt [B, 64] and t the CLS rows of project1's
+ * output, ldt elements apart (ntok·64 on the saved tensor).  The dropout mask is indexed as in the dense tensor of ntok tokens per image, so the
+ * regenerated mask (or keep_mask, uint8 [B, ntok, 64]) is the forward's; bit-identical to the CLS rows uia_mona_spatial_bwd writes.  The
+ * adapter_conv parameters get no gradient from this token. */
+int uia_mona_cls_bwd(void* stream, int dtype, int B, int ntok, const void* dd, const void* t, int64_t ldt, void* dt, float p_drop, uint64_t seed,
+                     const uint8_t* keep_mask);
 
 /* The WHOLE adapter forward of mona.py:319-362 (and :96-151, :198-253, :427-487) in one launch, one workgroup per image:
  *     y = x + project2(drop(gelu(spatial(project1(LN(x)·gamma + x·gammax)))))
@@ -473,6 +493,9 @@ int uia_embed_packed(void* stream, int rows, int D, int vocab, int max_pos, cons
  * rows whose id equals pad_id are skipped (padding_idx). */
 int uia_embed_bwd(void* stream, int rows, int D, int vocab, const int64_t* ids, const float* dx, float* dtable, int64_t pad_id);
 int uia_gather_rows(void* stream, int n, int D, const float* src, const int64_t* idx, float* dst);  /* model.py:372 */
+/* dst[r] = src[r·src_stride_bytes .. + row_bytes) for r < rows, dst compact: every stride-th row of a tensor of any element type (the CLS rows of a
+ * saved activation).  row_bytes, src_stride_bytes and both pointers are whole 16-byte units. */
+int uia_copy_rows(void* stream, int rows, int64_t row_bytes, const void* src, int64_t src_stride_bytes, void* dst);
 /* dst = (accumulate ? dst : 0) + src*keep/(1-p), keep from the counter hash of (seed, index): LoRA input dropout
  * (src/adapters/lora.py:82-83) and its backward (same seed). */
 int uia_dropout(void* stream, int dtype, size_t n, const void* src, void* dst, float p, uint64_t seed, int accumulate);

@@ -78,6 +78,20 @@ int uia_layernorm_bwd3(void* stream, int dtype, int M, int D, int64_t ldx, const
     return uia_layernorm_bwd3_launch((hipStream_t)stream, dtype, M, D, ldx, dy, x, x_hi, x_lo, (long)x_kb_rows, gamma, eps, dres, dres_hi, dres_lo, (long)dres_kb_rows, dx32, dxT,
                                      dx_lo);
 }
+int uia_layernorm_bwd_periodic(void* stream, int dtype, int M, int D, const void* dy, const float* x, const void* x_hi, const int8_t* x_lo, int64_t x_kb_rows,
+                               const float* gamma, float eps, const float* dres_rows, int period, float* dx32, void* dxT, int8_t* dx_lo) {
+    return uia_layernorm_bwd_periodic_launch((hipStream_t)stream, dtype, M, D, dy, x, x_hi, x_lo, (long)x_kb_rows, gamma, eps, dres_rows, period, dx32, dxT, dx_lo);
+}
+int uia_attn_bwd_cls(void* stream, int dtype, const uia_attn_desc* d) {
+    NEED(d, "uia_attn_bwd_cls");
+    return uia_attn_bwd_cls_launch((hipStream_t)stream, dtype, *d);
+}
+int uia_mona_cls_bwd(void* stream, int dtype, int B, int ntok, const void* dd, const void* t, int64_t ldt, void* dt, float p_drop, uint64_t seed, const uint8_t* keep_mask) {
+    return uia_mona_cls_bwd_launch((hipStream_t)stream, dtype, B, ntok, dd, t, (long)ldt, dt, p_drop, seed, keep_mask);
+}
+int uia_copy_rows(void* stream, int rows, int64_t row_bytes, const void* src, int64_t src_stride_bytes, void* dst) {
+    return uia_copy_rows_launch((hipStream_t)stream, rows, (long)row_bytes, src, (long)src_stride_bytes, dst);
+}
 int uia_cast(void* stream, int dtype, size_t n, const float* src, void* dst, float scale) { return uia_cast_launch((hipStream_t)stream, dtype, n, src, dst, scale); }
 int uia_transpose_cast(void* stream, int dtype, int rows, int cols, const float* src, void* dst) { return uia_transpose_cast_launch((hipStream_t)stream, dtype, rows, cols, src, dst); }
 int uia_pack_weights(void* stream, int dtype, int n, const uia_pack_desc* descs_device, int max_elems) { return uia_pack_weights_launch((hipStream_t)stream, dtype, n, descs_device, max_elems); }

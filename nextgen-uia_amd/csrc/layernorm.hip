@@ -69,12 +69,15 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(int M, int D, long ldx, con
 // THREE: every operand of the row, the three-byte residual gradient included (raw planes, three registers per float4, decoded at the end), is REQUESTED in the
 // first loop: the kernel lives on bytes in flight per wave, and a residual gradient fetched behind the three wave reductions was a second, exposed round trip
 // (126 -> 86 us per image-tower launch at 12 bytes per element; the fp32 form, 16 bytes per element, keeps its late request: 109 us).
-template <typename T, bool THREE, int NV>
+// PERIODIC: the residual gradient is compact fp32 rows [ceil(M / period), D] that belong to the rows r % period == 0 (token 0 of every sequence); all other rows
+// have none.  A compile-time variant like THREE, instantiated for the forms the CLS-sparse backward of the last image block uses.
+template <typename T, bool THREE, int NV, bool PERIODIC = false>
 __global__ __launch_bounds__(256, NV == 4 ? (THREE ? 3 : 5) : 1) void ln_bwd_kernel(int M, int D, long ldx, const T* __restrict__ dy, const float* __restrict__ x,
                                                       const float* __restrict__ gamma, float eps, const float* __restrict__ dres,
                                                       float* __restrict__ dx32, T* __restrict__ dxT,
                                                       const bf16_t* __restrict__ x_hi, const int8_t* __restrict__ x_lo, long x_kb_rows,
-                                                      const bf16_t* __restrict__ dres_hi, const int8_t* __restrict__ dres_lo, long dres_kb_rows, int8_t* __restrict__ dx_lo) {
+                                                      const bf16_t* __restrict__ dres_hi, const int8_t* __restrict__ dres_lo, long dres_kb_rows, int8_t* __restrict__ dx_lo,
+                                                      int period) {
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= M) return;
     const int nv = D >> 2;
@@ -83,7 +86,7 @@ __global__ __launch_bounds__(256, NV == 4 ? (THREE ? 3 : 5) : 1) void ln_bwd_ker
     f32x4 v[NV], g[NV];
     uint2 rhi[THREE ? NV : 1];
     unsigned rlo[THREE ? NV : 1];
-    const bool r3 = THREE && dres_lo != nullptr;
+    const bool r3 = THREE && !PERIODIC && dres_lo != nullptr;
     float s = 0.f;
 #pragma unroll
     for (int k = 0; k < NV; ++k) {
@@ -138,7 +141,9 @@ __global__ __launch_bounds__(256, NV == 4 ? (THREE ? 3 : 5) : 1) void ln_bwd_ker
         const int c = lane + 64 * k;
         if (c < nv) {
             f32x4 o = f32x4{0.f, 0.f, 0.f, 0.f};
-            if constexpr (THREE) {
+            if constexpr (PERIODIC) {
+                if (row % period == 0) o = load4(dres + (size_t)(row / period) * D + 4 * c);
+            } else if constexpr (THREE) {
                 if (r3) o = three_byte_decode4(rhi[k], rlo[k]);
                 else if (dres) o = load4(dres + (size_t)row * ldx + 4 * c);      // fp32 residual gradient beside a three-byte operand or result: the late load of the first form
             } else {
@@ -195,13 +200,39 @@ int uia_layernorm_bwd3_launch(hipStream_t stream, int dtype, int M, int D, long 
     const dim3 grid((M + 3) / 4), block(256);
 #define UIA_LN_BWD(TT, TH, NVV)                                                                                                              \
     hipLaunchKernelGGL((ln_bwd_kernel<TT, TH, NVV>), grid, block, 0, stream, M, D, ldx, (const TT*)dy, x, gamma, eps, dres, dx32, (TT*)dxT,          \
-                       (const bf16_t*)x_hi, x_lo, x_kb_rows, (const bf16_t*)dres_hi, dres_lo, dres_kb_rows, dx_lo)
+                       (const bf16_t*)x_hi, x_lo, x_kb_rows, (const bf16_t*)dres_hi, dres_lo, dres_kb_rows, dx_lo, 0)
     const bool narrow = D <= 768;
     if (dtype == UIA_BF16 && three) { if (narrow) UIA_LN_BWD(bf16_t, true, 3); else UIA_LN_BWD(bf16_t, true, 4); }
     else if (dtype == UIA_BF16) { if (narrow) UIA_LN_BWD(bf16_t, false, 3); else UIA_LN_BWD(bf16_t, false, 4); }
     else if (dtype == UIA_F32) { if (narrow) UIA_LN_BWD(float, false, 3); else UIA_LN_BWD(float, false, 4); }
 #undef UIA_LN_BWD
     else { uia_set_error("uia_layernorm_bwd: bad dtype %d", dtype); return -1; }
+    UIA_CHECK_LAUNCH();
+    return 0;
+}
+
+int uia_layernorm_bwd_periodic_launch(hipStream_t stream, int dtype, int M, int D, const void* dy, const float* x, const void* x_hi, const int8_t* x_lo, long x_kb_rows,
+                                      const float* gamma, float eps, const float* dres_rows, int period, float* dx32, void* dxT, int8_t* dx_lo) {
+    UIA_CHECK_ARG(M > 0 && D > 0 && D % 4 == 0 && D <= 1024 && period > 0, "uia_layernorm_bwd_periodic: unsupported shape M=%d D=%d period=%d", M, D, period);
+    UIA_CHECK_ARG(dy && (x || (x_hi && x_lo)) && gamma && dres_rows && (dx32 || dxT), "uia_layernorm_bwd_periodic: null tensor");
+    UIA_CHECK_ARG(((uintptr_t)dres_rows % 16) == 0, "uia_layernorm_bwd_periodic: dres_rows must be 16-byte aligned");
+    UIA_CHECK_ARG(dtype == UIA_BF16 || dtype == UIA_F32, "uia_layernorm_bwd_periodic: bad dtype %d", dtype);
+    if (dtype == UIA_BF16)
+        UIA_CHECK_ARG(dx_lo && dxT && ((uintptr_t)dxT % 8) == 0 && ((uintptr_t)dx_lo % 4) == 0, "uia_layernorm_bwd_periodic: the bf16 form writes a three-byte result (dxT + dx_lo)");
+    else
+        UIA_CHECK_ARG(!dx_lo && !x_lo && !x_hi, "uia_layernorm_bwd_periodic: three-byte tensors need bf16");
+    UIA_CHECK_ARG(!x_lo || (x_hi && !x && (x_kb_rows == 0 || (x_kb_rows >= M && D % 32 == 0)) && ((uintptr_t)x_hi % 8) == 0 && ((uintptr_t)x_lo % 4) == 0),
+                  "uia_layernorm_bwd_periodic: x as a three-byte tensor needs x_hi + x_lo (and no fp32 x), a K-blocked hi plane of at least M rows and D a multiple of 32");
+    UIA_CHECK_ARG(x_lo || x_kb_rows == 0, "uia_layernorm_bwd_periodic: x_kb_rows without a three-byte x");
+    const dim3 grid((M + 3) / 4), block(256);
+    const long ldx = D;
+#define UIA_LN_BWD_P(TT, TH, NVV)                                                                                                                    \
+    hipLaunchKernelGGL((ln_bwd_kernel<TT, TH, NVV, true>), grid, block, 0, stream, M, D, ldx, (const TT*)dy, x, gamma, eps, dres_rows, dx32, (TT*)dxT, \
+                       (const bf16_t*)x_hi, x_lo, x_kb_rows, (const bf16_t*)nullptr, (const int8_t*)nullptr, 0L, dx_lo, period)
+    const bool narrow = D <= 768;
+    if (dtype == UIA_BF16) { if (narrow) UIA_LN_BWD_P(bf16_t, true, 3); else UIA_LN_BWD_P(bf16_t, true, 4); }
+    else { if (narrow) UIA_LN_BWD_P(float, false, 3); else UIA_LN_BWD_P(float, false, 4); }
+#undef UIA_LN_BWD_P
     UIA_CHECK_LAUNCH();
     return 0;
 }

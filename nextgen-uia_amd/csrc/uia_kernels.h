@@ -21,6 +21,12 @@ int uia_layernorm_bwd_launch(hipStream_t stream, int dtype, int M, int D, long l
 int uia_layernorm_bwd3_launch(hipStream_t stream, int dtype, int M, int D, long ldx, const void* dy, const float* x, const void* x_hi, const int8_t* x_lo,
                               long x_kb_rows, const float* gamma, float eps, const float* dres, const void* dres_hi, const int8_t* dres_lo, long dres_kb_rows,
                               float* dx32, void* dxT, int8_t* dx_lo);
+int uia_layernorm_bwd_periodic_launch(hipStream_t stream, int dtype, int M, int D, const void* dy, const float* x, const void* x_hi, const int8_t* x_lo, long x_kb_rows,
+                                      const float* gamma, float eps, const float* dres_rows, int period, float* dx32, void* dxT, int8_t* dx_lo);
+int uia_attn_bwd_cls_launch(hipStream_t stream, int dtype, const UiaAttnParams& p);
+int uia_mona_cls_bwd_launch(hipStream_t stream, int dtype, int B, int ntok, const void* dd, const void* t, long ldt, void* dt, float p_drop, uint64_t seed,
+                            const uint8_t* keep_mask);
+int uia_copy_rows_launch(hipStream_t stream, int rows, long row_bytes, const void* src, long src_stride_bytes, void* dst);
 int uia_lora_rank_update_launch(hipStream_t stream, int dtype, const uia_lora_rank_desc& p);
 int uia_ln_lora_down_launch(hipStream_t stream, int dtype, const uia_ln_lora_desc& p);
 int uia_cast_launch(hipStream_t stream, int dtype, size_t n, const float* src, void* dst, float scale);

@@ -188,6 +188,10 @@ PROTOTYPES = {
     "uia_embed_bwd": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int64]),
     "uia_embed_packed": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]),
     "uia_gather_rows": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp]),
+    "uia_copy_rows": (C.c_int, [vp, C.c_int, i64, vp, i64, vp]),
+    "uia_attn_bwd_cls": (C.c_int, [vp, C.c_int, C.POINTER(AttnDesc)]),
+    "uia_mona_cls_bwd": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, i64, vp, f32, C.c_uint64, vp]),
+    "uia_layernorm_bwd_periodic": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, i64, vp, f32, vp, C.c_int, vp, vp, vp]),
 }
 
 _lib = None

@@ -25,8 +25,8 @@ from ._lib import UiaError
 # The hand-offs that carry tensors BESIDE autograd between the Functions below (T copies of gradients, three-byte tokens, rows + row sums of a
 # folded LayerNorm) and the rules for handing them out live in uia_hip.handoff; these are its names as the engine, the models and the tests use
 # them.  MonaFn and VitBlockFn call them through THIS module's globals (tests replace publish_grad3 / publish_fwd3 here to count calls).
-from .handoff import (Resid3, _g3_partner_feeds, fwd3_of, grad3_decode, grad3_of, grad_resid3_enabled, hook_free, linear_chain,      # noqa: F401
-                      publish_fwd3, publish_grad3, publish_rows, publish_t_copy, set_grad_resid3, t_copy_of, take_rows, zero_sums)
+from .handoff import (ClsGrad, Resid3, _g3_partner_feeds, cls_grad_of, fwd3_of, grad3_decode, grad3_of, grad_resid3_enabled, hook_free, linear_chain,      # noqa: F401
+                      publish_cls_grad, publish_fwd3, publish_grad3, publish_rows, publish_t_copy, set_cls_grad, set_grad_resid3, t_copy_of, take_rows, zero_sums)
 from .handoff import clear as clear_t_copies      # noqa: F401
 
 _STATE = {"dtype": torch.bfloat16, "seed": 0x5EED, "calls": 0, "fwd_resid3": os.environ.get("UIA_FWD_RESID3", "1") != "0"}
@@ -504,10 +504,54 @@ class MonaFn(torch.autograd.Function):
         ctx.meta = (variant, hw, p_drop, seed, names, keep_mask is not None)
         ctx.direct_params = tuple(params) if direct else None      # the Parameter objects themselves: .grad is looked up at BACKWARD time
         ctx.g3_out = dt == torch.bfloat16 and _g3_partner_feeds(x)
+        # a CLS-sparse gradient (ClsGrad) is taken when the block in front takes one too: the whole tail of the tower then runs on the CLS rows
+        front = handoff.partner_node(x)
+        ctx.cls_ok = u is not None and type(front).__name__ == "VitBlockFnBackward" and handoff.takes_cls_grad(x)
         return y
 
     @staticmethod
+    def backward_cls(ctx, cg):
+        """backward on a ClsGrad: the gradient is zero outside token 0 of every image and every stage but the spatial operator works row by row, so the same
+        sequence runs at M = B on the CLS rows of the saved x, u, t, d.  The CLS token bypasses the spatial operator: its parameters get exactly zero from here."""
+        variant, hw, p_drop, seed, names, has_mask = ctx.meta
+        x, u, t, d, keep_mask, *params = ctx.saved_tensors
+        keep_mask = keep_mask if has_mask else None
+        P = dict(zip(names, params))
+        B, N, D = x.shape
+        dt, bott = u.dtype, t.shape[1]
+        dy = cg.rows32
+        dy_t = dy if dt == torch.float32 else (cg.rows_t if cg.rows_t is not None else t_copy_of(dy, dt))
+        direct = ctx.direct_params is not None and all(_is_flat_grad(p) for p in ctx.direct_params)
+        G = ({k: p.grad for k, p in zip(names, ctx.direct_params)} if direct
+             else {k: torch.zeros_like(v, dtype=torch.float32) for k, v in P.items()})
+        cls_rows = lambda a: a.view(B, N * a.shape[1])[:, :a.shape[1]]           # row b·N of a saved [M, W] activation, read through the row stride
+        side = _wgrad_side_stream(x.device) if _STATE.get("wgrad_side_stream", False) else None
+        w2t = WEIGHTS.get(P["project2.weight"], dt, transpose=True)
+        dd = _empty((B, bott), dt, x)
+        _wgrad_beside(side, lambda: ops.gemm(dy_t, w2t, out_t=dd), dy_t, cls_rows(d), G["project2.weight"], G["project2.bias"])
+        dtt = _empty((B, bott), dt, x)
+        ops.mona_cls_bwd(B, N, dd, t, dtt, p_drop=p_drop, seed=seed, keep_mask=keep_mask)
+        w1t = WEIGHTS.get(P["project1.weight"], dt, transpose=True)
+        fuse_du = x.is_cuda and ops.mona_pre_bwd_du_ok(B, D, bott, dt)
+        du = None if fuse_du else _empty((B, D), dt, x)
+        _wgrad_beside(side, None if fuse_du else (lambda: ops.gemm(dtt, w1t, out_t=du)), dtt, cls_rows(u), G["project1.weight"], G["project1.bias"])
+        need_dx = ctx.needs_input_grad[0]
+        x_cls = ops.copy_rows(x.view(B * N, D), N, _empty((B, D), torch.float32, x))
+        dx = _empty((B, D), torch.float32, x) if need_dx else None
+        dx_t = _empty((B, D), dt, x) if (need_dx and dt != torch.float32) else None
+        w1t_rows = (dtt, w1t.row if isinstance(w1t, ops.PackedW) else w1t) if fuse_du else None
+        ops.mona_pre_bwd(du, x_cls, dy if need_dx else None, P["norm.weight"], P["norm.bias"], P["gamma"], P["gammax"], dx, dx_t,
+                         G["gamma"], G["gammax"], G["norm.weight"], G["norm.bias"], dt_w1t=w1t_rows)
+        if need_dx:
+            dx = publish_cls_grad(x.shape, x.device, dx, dx_t) if ctx.cls_ok else ClsGrad(dx, dx_t, N).decode()
+        grads = tuple(None if direct else (G[k] if ctx.needs_input_grad[7 + i] else None) for i, k in enumerate(names))
+        return (dx, None, None, None, None, None, None) + grads
+
+    @staticmethod
     def backward(ctx, dy):
+        cg = cls_grad_of(dy)                                 # a CLS-sparse gradient from the head behind this adapter
+        if cg is not None:
+            return MonaFn.backward_cls(ctx, cg)
         variant, hw, p_drop, seed, names, has_mask = ctx.meta
         x, u, t, d, keep_mask, *params = ctx.saved_tensors
         keep_mask = keep_mask if has_mask else None
@@ -722,10 +766,64 @@ class VitBlockFn(torch.autograd.Function):
             ctx.xshape = (B, N, D)
             ctx.spec = spec
             ctx.g3_out = dt == torch.bfloat16 and _g3_partner_feeds(x)
+            # a CLS-sparse gradient (ClsGrad) is taken by the unmasked single-pass attention on 64-wide heads with an fp32 x1
+            ctx.cls_ok = spec.mask is None and N <= ATTN_SINGLE_PASS_MAX and D == 64 * spec.heads and not r3 and handoff.cls_grad_enabled()
         return x2
 
     @staticmethod
+    def backward_cls(ctx, cg):
+        """backward on a ClsGrad: the MLP half, the LayerNorm-2 backward and the projection's data gradient work row by row and run at M = B on the CLS rows; the
+        attention backward has one non-zero query row per head (ops.attn_bwd_cls) and makes the gradient dense; from the QKV data gradient on everything is the
+        dense backward, with dx1 — still CLS-sparse — entering the LayerNorm-1 backward as B rows (ops.layernorm_bwd_periodic)."""
+        xin, qkv, a, lse, x1, pre = handoff.restore_layout(ctx.saved_tensors, ctx.layout)
+        x3_in = isinstance(xin, Resid3)
+        x = xin.lo if x3_in else xin
+        spec = ctx.spec
+        B, N, D = ctx.xshape
+        M, dt = B * N, qkv.dtype
+        F = pre.shape[1]
+        dy = cg.rows32
+        dy_t = dy if dt == torch.float32 else (cg.rows_t if cg.rows_t is not None else t_copy_of(dy, dt))
+        pre_cls = ops.copy_rows(pre, N, _empty((B, F), dt, x))
+        dpre = _empty((B, F), dt, x)
+        ops.gemm(dy_t, WEIGHTS.get(spec.fc2[0], dt, transpose=True), dact=spec.act, aux_in=pre_cls, out_t=dpre)
+        dh = _empty((B, D), dt, x)
+        ops.gemm(dpre, WEIGHTS.get(spec.fc1[0], dt, transpose=True), out_t=dh)
+        x1_cls = ops.copy_rows(x1, N, _empty((B, D), torch.float32, x))
+        dx1 = _empty((B, D), torch.float32, x)
+        dx1_t = _empty((B, D), dt, x) if dt != torch.float32 else dx1
+        ops.layernorm_bwd(dh, x1_cls, spec.ln2[0], spec.eps, dres=dy, dx32=dx1, dx_t=dx1_t if dt != torch.float32 else None)
+        da = dh
+        ops.gemm(dx1_t, WEIGHTS.get(spec.proj[0], dt, transpose=True), out_t=da)
+        dqkv = _attn_act(M, 3 * D, dt, x, D)                                          # read by the QKV dgrad GEMM only
+        if ops.is_kb(dqkv):
+            ops.attn_bwd_cls(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], a, da, lse, dqkv, None, None, B, spec.heads, N)
+        else:
+            ops.attn_bwd_cls(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], a, da, lse, dqkv[:, :D], dqkv[:, D:2 * D], dqkv[:, 2 * D:], B, spec.heads, N)
+        dh1 = _empty((M, D), dt, x)
+        ops.gemm(dqkv, WEIGHTS.get(spec.qkv[0], dt, transpose=True), out_t=dh1)
+        xrows = xin if x3_in else x.view(M, D)
+        if getattr(ctx, "g3_out", False):
+            dx_t = _empty((M, D), dt, x)
+            dlo = torch.empty(M, D, device=x.device, dtype=torch.int8)
+            ops.layernorm_bwd_periodic(dh1, xrows, spec.ln1[0], spec.eps, dx1, N, dx_t=dx_t, dx_lo=dlo)
+            return publish_grad3((B, N, D), x.device, dx_t, dlo), None
+        dx = torch.empty(B, N, D, device=x.device, dtype=torch.float32)
+        if dt == torch.float32:
+            ops.layernorm_bwd_periodic(dh1, xrows, spec.ln1[0], spec.eps, dx1, N, dx32=dx.view(M, D))
+            return dx, None
+        dx_t = _empty((M, D), dt, x)                          # bf16 and an fp32 consumer in front: the plain launch on the zero-padded rows
+        ops.layernorm_bwd(dh1, xrows, spec.ln1[0], spec.eps, dres=ClsGrad(dx1, None, N).decode().view(M, D), dx32=dx.view(M, D), dx_t=dx_t)
+        publish_t_copy(dx, dx_t)
+        return dx, None
+
+    @staticmethod
     def backward(ctx, dx2):
+        cg = cls_grad_of(dx2)                                         # a CLS-sparse gradient from the head or the adapter behind this block
+        if cg is not None:
+            if getattr(ctx, "cls_ok", False):
+                return VitBlockFn.backward_cls(ctx, cg)
+            dx2 = cg.decode()                                         # not a block the sparse path covers: the dense gradient, fp32 from here
         g3 = grad3_of(dx2)                                            # a three-byte gradient from the adapter behind this block: Resid3(T copy, possibly K-blocked; low bytes)
         xin, qkv, a, lse, x1, pre = handoff.restore_layout(ctx.saved_tensors, ctx.layout)
         x3_in, r3 = isinstance(xin, Resid3), isinstance(x1, Resid3)   # three-byte block input (set_fwd_resid3) / three-byte x1 (set_block_resid3)
@@ -960,6 +1058,7 @@ class ClsHeadFn(torch.autograd.Function):
         ops.gemm(h, WEIGHTS.get(w, dt, transpose=w_is_in_out), out32=feat)
         ctx.save_for_backward(x, ln_w)
         ctx.meta = (eps, w, w_is_in_out, dt)
+        ctx.cls_out = handoff.takes_cls_grad(x, in_chain=False)      # the Function that produced x runs its backward on the CLS rows (handoff.ClsGrad)
         return feat
 
     @staticmethod
@@ -984,6 +1083,12 @@ class ClsHeadFn(torch.autograd.Function):
             dh_t = _empty((B, D), dt, x)
             ops.cast(dh, dh_t)
             dh = dh_t
+        if getattr(ctx, "cls_out", False):                  # no dense tensor, nothing filled: the B rows travel as they are
+            x_cls = ops.copy_rows(x.view(B * N, D), N, _empty((B, D), torch.float32, x))
+            rows32 = _empty((B, D), torch.float32, x)
+            rows_t = _empty((B, D), dt, x) if dt != torch.float32 else None
+            ops.layernorm_bwd(dh, x_cls, ln_w, eps, dx32=rows32, dx_t=rows_t)
+            return publish_cls_grad(x.shape, x.device, rows32, rows_t), None, None, None, None, None
         dx = torch.zeros_like(x)
         dx_t = torch.zeros(B * N, D, device=x.device, dtype=dt) if dt != torch.float32 else None
         ops.layernorm_bwd(dh, x, ln_w, eps, dx32=dx, dx_t=dx_t, rows=B, ldx=N * D)

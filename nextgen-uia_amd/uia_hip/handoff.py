@@ -3,12 +3,13 @@
   T copies of fp32 gradients       publish_t_copy / t_copy_of     data pointer + version + storage, 256 deep
   three-byte gradient tokens       publish_grad3 / grad3_of       token address, pool of 64
   three-byte forward tokens        publish_fwd3 / fwd3_of         token address, pool of 256
+  CLS-sparse gradient tokens       publish_cls_grad / cls_grad_of token address, pool of 64
   T rows + row sums (LN fold)      publish_rows / take_rows       raw stream, one slot
   zeroed row-sum arena             zero_sums                      raw stream, 48 slices
 
 with the rules that say when a token may be handed out (linear_chain, hook_free, _g3_partner_feeds, set_grad_resid3), the named type of a
-three-byte value (Resid3) and the one place that knows how a K-blocked activation goes through save_for_backward (save_layout / restore_layout).
-clear() drops all five channels.  Nothing here launches a kernel except the cast of a T copy that was not published and Resid3.decode().
+three-byte value (Resid3), of a CLS-sparse gradient (ClsGrad) and the one place that knows how a K-blocked activation goes through save_for_backward (save_layout / restore_layout).
+clear() drops all six channels.  Nothing here launches a kernel except the cast of a T copy that was not published, Resid3.decode() and ClsGrad.decode().
 """
 from typing import NamedTuple
 
@@ -16,7 +17,7 @@ import torch
 
 from . import ops
 
-_STATE = {"chain_depth": 0, "fwd3_next_plain": False, "grad_resid3": False}
+_STATE = {"chain_depth": 0, "fwd3_next_plain": False, "grad_resid3": False, "cls_grad": True}
 
 
 # ------------------------------------------------------------------------------------------------ three-byte values
@@ -40,6 +41,21 @@ class Fwd3(NamedTuple):
     @property
     def resid3(self):
         return Resid3(self.hi, self.lo)
+
+
+class ClsGrad(NamedTuple):
+    """A [B, N, D] residual-stream gradient that is zero outside token 0 of every image (the gradient a CLS-pooling head returns): the B non-zero rows in
+    fp32 and, in bf16 mode, their T copy.  MonaFn.backward and VitBlockFn.backward run their row-wise stages on these rows alone."""
+    rows32: torch.Tensor
+    rows_t: object
+    tokens: int
+
+    def decode(self):
+        """The dense fp32 [B, N, D] gradient: zeros plus a scatter (slow path of a consumer that cannot take the rows: torch ops)."""
+        B, D = self.rows32.shape
+        dense = self.rows32.new_zeros(B, self.tokens, D)
+        dense[:, 0] = self.rows32
+        return dense
 
 
 def save_layout(*values):
@@ -109,6 +125,8 @@ class TokenRegistry:
 GRAD3 = TokenRegistry(64)
 # Forward twin: a residual-stream VALUE handed from MonaFn to the next block's VitBlockFn as (hi plane, low bytes, row sums).
 FWD3 = TokenRegistry(256)
+# A CLS-sparse gradient from the head to the last adapter / block of a tower, and from that adapter to the block in front of it (ClsGrad).
+CLSG = TokenRegistry(64)
 _G3_VIEWS = ("PermuteBackward0", "ViewBackward0", "UnsafeViewBackward0", "TransposeBackward0", "AliasBackward0", "ReshapeAliasBackward0")
 _G3_PARTNERS = ("MonaFnBackward", "VitBlockFnBackward")
 
@@ -134,6 +152,26 @@ def publish_fwd3(shape, device, hi, lo, sums):
 def fwd3_of(x):
     """Fwd3(hi, lo, sums) when x is a token of publish_fwd3 (consumed), else None.  Call BEFORE anything touches x's values."""
     return FWD3.take(x)
+
+
+def publish_cls_grad(shape, device, rows32, rows_t):
+    """Register the CLS rows of a gradient of `shape` = [B, N, D] and return the token autograd carries in its place."""
+    return CLSG.publish(shape, device, ClsGrad(rows32, rows_t, shape[1]))
+
+
+def cls_grad_of(g):
+    """ClsGrad when g is a token of publish_cls_grad (consumed), else None.  Call BEFORE anything touches g's values."""
+    return CLSG.take(g)
+
+
+def set_cls_grad(flag):
+    """Switch of the CLS-sparse backward (default on; off: the head hands on the dense gradient it always did).  It only ever applies where three-byte gradient
+    tokens may travel: the per-step opt-in set_grad_resid3 is on and the head's input comes straight from a MonaFn / VitBlockFn."""
+    _STATE["cls_grad"] = bool(flag)
+
+
+def cls_grad_enabled():
+    return _STATE["cls_grad"] and _STATE["grad_resid3"]
 
 
 def set_grad_resid3(flag):
@@ -186,21 +224,33 @@ def hook_free(*modules):
     return True
 
 
-def _g3_partner_feeds(x):
-    """True when x is the output of a MonaFn / VitBlockFn seen through view nodes only: the gradient this Function returns for x goes to that Function's backward."""
-    if not _STATE["grad_resid3"] or _STATE["chain_depth"] <= 0:
-        return False
+def partner_node(x, in_chain=True):
+    """The backward node of the MonaFn / VitBlockFn whose output x is, seen through view nodes only (the gradient a Function returns for x goes to that node's
+    backward and nowhere else), or None.  in_chain = False: the caller runs behind the tower's block loop (the CLS head: linear_chain has closed by then)."""
+    if not _STATE["grad_resid3"] or (in_chain and _STATE["chain_depth"] <= 0):
+        return None
     fn = x.grad_fn
     for _ in range(8):
         if fn is None:
-            return False
+            return None
         name = type(fn).__name__
         if name in _G3_PARTNERS:
-            return True
+            return fn
         if name not in _G3_VIEWS or len(fn.next_functions) != 1:
-            return False
+            return None
         fn = fn.next_functions[0][0]
-    return False
+    return None
+
+
+def _g3_partner_feeds(x):
+    """True when x is the output of a MonaFn / VitBlockFn seen through view nodes only: the gradient this Function returns for x goes to that Function's backward."""
+    return partner_node(x) is not None
+
+
+def takes_cls_grad(x, in_chain=True):
+    """True when the gradient returned for x may be a ClsGrad token: the switch and the per-step opt-in are on, x comes straight from a MonaFn / VitBlockFn, and
+    that Function's forward said (ctx.cls_ok) that its backward runs on the CLS rows."""
+    return cls_grad_enabled() and bool(getattr(partner_node(x, in_chain), "cls_ok", False))
 
 
 # ------------------------------------------------------------------------------------------------ T copies
@@ -284,3 +334,4 @@ def clear():
     _SUMS_ARENA.clear()
     GRAD3.clear()
     FWD3.clear()
+    CLSG.clear()

@@ -944,6 +944,34 @@ def attn_bwd(q, k, v, out, dout, lse, dq, dk, dv, B, H, L, mask=None, keylen=Non
         check(lib().uia_attn_bwd(_stream(), _code(q.dtype), C.byref(d)), "uia_attn_bwd")
 
 
+def attn_bwd_cls(q, k, v, out, dout, lse, dq, dk, dv, B, H, L, mask=None, scale=None):
+    """uia_attn_bwd_cls: attention backward for a gradient that is zero outside token 0 of every sequence.  dout [B, H*64] holds the CLS rows only;
+    q / k / v / out / lse / dq / dk / dv as attn_bwd (dq K-blocked: the fused gradient, dk = dv = None).  Every element of dq, dk, dv is written.
+    Head dim 64, no mask."""
+    if mask not in (None, "none"):
+        raise UiaError(f"attn_bwd_cls: mask {mask!r}: the CLS-query backward takes unmasked attention only")
+    d = _attn_desc(q, k, v, out, lse, B, H, L, None, None, scale)
+    if d.dh != 64:
+        raise UiaError(f"attn_bwd_cls: head dim {d.dh}, only 64 is supported")
+    if dout.dim() != 2 or dout.shape[0] != B or dout.shape[1] != H * 64 or dout.stride(1) != 1 or dout.dtype != q.dtype:
+        raise UiaError(f"attn_bwd_cls: dout must be [{B}, {H * 64}] {q.dtype} rows (one per sequence), got {tuple(dout.shape)} {dout.dtype}")
+    if lse is None or lse.dtype != torch.float32 or not lse.is_contiguous() or lse.numel() != B * H * L:
+        raise UiaError(f"attn_bwd_cls: lse must be a contiguous fp32 [{B}, {H}, {L}] tensor")
+    d.dout, d.lddo = _p(dout), dout.stride(0)
+    if is_kb(dq):
+        rows, cols, d.dqkv_kb_rows = _kb_dims(dq, "attention dqkv")
+        if rows < B * L or cols != 3 * H * 64 or q.dtype != torch.bfloat16 or dk is not None or dv is not None:
+            raise UiaError(f"attention dqkv (K-blocked {tuple(dq.t.shape)}) must hold [{B * L}, {3 * H * 64}] bf16 with head dim 64, dk = dv = None")
+        part = (H * 64 // kb_group(q.dtype)) * d.dqkv_kb_rows * kb_group(q.dtype) * dq.t.element_size()
+        d.dq, d.dk, d.dv, d.ld_dqkv = dq.t.data_ptr(), dq.t.data_ptr() + part, dq.t.data_ptr() + 2 * part, cols
+    else:
+        for name, t in (("dq", dq), ("dk", dk), ("dv", dv)):
+            if t.dtype != q.dtype or t.dim() != 2 or t.shape[0] < B * L or t.shape[1] != H * 64 or t.stride(1) != 1 or t.stride(0) != dq.stride(0):
+                raise UiaError(f"attn_bwd_cls: {name} must be [{B * L}, {H * 64}] {q.dtype} rows sharing one row stride, got {tuple(t.shape)} {t.dtype}")
+        d.dq, d.dk, d.dv, d.ld_dqkv = _p(dq), _p(dk), _p(dv), dq.stride(0)
+    check(lib().uia_attn_bwd_cls(_stream(), _code(q.dtype), C.byref(d)), "uia_attn_bwd_cls")
+
+
 def layernorm_fwd(x, gamma, beta, eps, y_t=None, y32=None, rows=None, ldx=None, stats=None):
     """x fp32 [rows, D] (row stride ldx); y_t (bf16|fp32) and/or y32 compact [rows, D]; stats fp32 [rows, 2] receives (mean, rstd)."""
     D = gamma.numel()
@@ -1002,6 +1030,28 @@ def layernorm_bwd(dy, x, gamma, eps, dres=None, dx32=None, dx_t=None, rows=None,
                                        None if isinstance(dres, tuple) else _p(dres), _p(r_hi), _p(r_lo), r_kb, _p(dx32), _p(dx_t), _p(dx_lo)), "uia_layernorm_bwd3")
         return
     check(lib().uia_layernorm_bwd(_stream(), _code(dy.dtype), rows, D, ldx, _p(dy), _p(x), _p(gamma), eps, _p(dres), _p(dx32), _p(dx_t)), "uia_layernorm_bwd")
+
+
+def layernorm_bwd_periodic(dy, x, gamma, eps, dres_rows, period, dx32=None, dx_t=None, dx_lo=None):
+    """layernorm_bwd whose residual gradient exists on rows r % period == 0 only: dres_rows fp32 [ceil(M / period), D] compact (uia_layernorm_bwd_periodic).
+    bf16: the result is three-byte (dx_t, dx_lo), x fp32 or a (hi, lo) tuple; fp32: dx32 and / or dx_t, x fp32.  Bit-identical to layernorm_bwd on the zero-padded rows."""
+    D = gamma.numel()
+    M = dy.numel() // D
+    nrows = (M + period - 1) // period
+    _dense(dres_rows, "layernorm_bwd_periodic: dres_rows", _F32, nrows * D, align=16)
+    x_hi, x_lo = x if isinstance(x, tuple) else (None, None)
+    x_kb = 0
+    if is_kb(x_hi):
+        kr, kc, x_kb = _kb_dims(x_hi, "layernorm_bwd_periodic x hi plane")
+        if kr < M or kc != D:
+            raise UiaError(f"layernorm_bwd_periodic: K-blocked x hi plane {tuple(x_hi.t.shape)} does not hold [{M}, {D}]")
+        x_hi = x_hi.t
+    for name, t, dt_ in (("dy", dy, dy.dtype), ("x", None if isinstance(x, tuple) else x, torch.float32), ("x hi", x_hi, torch.bfloat16), ("x lo", x_lo, torch.int8),
+                         ("dx32", dx32, torch.float32), ("dx_t", dx_t, dy.dtype), ("dx_lo", dx_lo, torch.int8)):
+        if t is not None and (t.dtype != dt_ or not t.is_contiguous() or t.numel() < M * D):
+            raise UiaError(f"layernorm_bwd_periodic: {name} must be a contiguous {dt_} tensor of at least [{M}, {D}], got {tuple(t.shape)} {t.dtype}")
+    check(lib().uia_layernorm_bwd_periodic(_stream(), _code(dy.dtype), M, D, _p(dy), None if isinstance(x, tuple) else _p(x), _p(x_hi), _p(x_lo), x_kb, _p(gamma), eps,
+                                           _p(dres_rows), int(period), _p(dx32), _p(dx_t), _p(dx_lo)), "uia_layernorm_bwd_periodic")
 
 
 def cast(src, dst, scale=1.0):
@@ -1152,6 +1202,18 @@ def gather_rows(src, idx, dst):
     check(lib().uia_gather_rows(_stream(), idx.numel(), src.shape[-1], _p(src), _p(idx), _p(dst)), "uia_gather_rows")
 
 
+def copy_rows(src, stride_rows, dst):
+    """dst[r] = src[r * stride_rows] for the rows of dst: every stride_rows-th row of a contiguous [M, W] tensor of any dtype (uia_copy_rows;
+    the CLS rows of a saved activation: stride_rows = tokens per image).  Rows are whole 16-byte units."""
+    if src.dim() != 2 or dst.dim() != 2 or not src.is_contiguous() or not dst.is_contiguous() or src.dtype != dst.dtype or src.shape[1] != dst.shape[1]:
+        raise UiaError(f"copy_rows: contiguous 2-D tensors of one dtype and width are required, got {tuple(src.shape)} {src.dtype} -> {tuple(dst.shape)} {dst.dtype}")
+    rows, row_bytes = dst.shape[0], src.shape[1] * src.element_size()
+    _require(rows > 0 and stride_rows > 0 and (rows - 1) * stride_rows < src.shape[0], f"copy_rows: {rows} rows {stride_rows} apart do not fit the {src.shape[0]} rows of src")
+    _require(row_bytes % 16 == 0 and src.data_ptr() % 16 == 0 and dst.data_ptr() % 16 == 0, "copy_rows: rows must be whole, aligned 16-byte units")
+    check(lib().uia_copy_rows(_stream(), rows, row_bytes, _p(src), row_bytes * stride_rows, _p(dst)), "uia_copy_rows")
+    return dst
+
+
 # ------------------------------------------------------------------------------------------- Mona
 _SPATIAL_KEYS = ("conv1_w", "conv1_b", "conv2_w", "conv2_b", "conv3_w", "conv3_b", "proj_w", "proj_b", "freq", "ne1_w", "ne1_b", "ne3_w", "ne3_b")
 
@@ -1293,6 +1355,17 @@ def mona_spatial_bwd(variant, B, h, w, t, params, dd, dt, grads, p_drop=0.0, see
         if v is not None:
             setattr(d, "g_" + k, _p(v))
     check(lib().uia_mona_spatial_bwd(_stream(), _code(t.dtype), C.byref(d)), "uia_mona_spatial_bwd")
+
+
+def mona_cls_bwd(B, ntok, dd, t, dt, p_drop=0.0, seed=0, keep_mask=None):
+    """The CLS token's share of mona_spatial_bwd (uia_mona_cls_bwd): dd, dt compact [B, 64]; t the forward's [B * ntok, 64] tensor, read at rows b * ntok;
+    the dropout mask (seed or keep_mask uint8 [B, ntok, 64]) is indexed as in the dense tensor.  No parameter gradients: the token bypasses the spatial operator."""
+    for name, x_, n in (("dd", dd, B * 64), ("dt", dt, B * 64), ("t", t, B * ntok * 64)):
+        _dense(x_, f"mona_cls_bwd: {name}", (t.dtype,), n, align=2)
+    if keep_mask is not None:
+        _dense(keep_mask, "mona_cls_bwd: keep_mask", (torch.uint8,), B * ntok * 64)
+    check(lib().uia_mona_cls_bwd(_stream(), _code(t.dtype), B, ntok, _p(dd), _p(t), ntok * 64, _p(dt), float(p_drop), int(seed) & 0xFFFFFFFFFFFFFFFF, _p(keep_mask)),
+          "uia_mona_cls_bwd")
 
 
 # ------------------------------------------------------------------------------------------- loss / optimiser / comm
