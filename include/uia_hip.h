@@ -449,6 +449,27 @@ int uia_binary_cls_stats(void* stream, int N, const float* p1, const int64_t* la
 size_t uia_surface_distances_workspace_bytes(int B, int H, int W);
 int uia_surface_distances(void* stream, int B, int H, int W, const float* logits, const float* label, float percentile, void* ws, size_t ws_bytes,
                           double* hd, double* asd);
+/* Image-text retrieval evaluation (the call sites of reference src/models/biomedclip/retrieval.py:329; the reference never shipped its metric module, so
+ * these definitions are this build's).  img, txt fp32 [N,E] row-major contiguous, 16-byte aligned: N feature pairs; 1 <= N <= 2^24, E % 4 == 0,
+ * 4 <= E <= 4096.  Scores s_ij = <a_i, b_j> with a_i = img_i / max(||img_i||, 1e-12), b_j likewise from txt_j (F.normalize) when normalize != 0, else
+ * the raw rows; the product runs on the exact fp32 MFMA (a k-ordered fmaf chain from 0), and the bits of s_ij depend only on the values of row i of img
+ * and row j of txt, never on their place in a tile or the grid: equal pairs of rows give exact ties.  d_i = s_ii comes from the same tile path.
+ * Outputs int32 [N] each, for image i: gt_i2t[i] = #{j != i : s_ij > d_i}, eq_i2t[i] = #{j != i : s_ij == d_i}; for text j: gt_t2i[j] =
+ * #{i != j : s_ij > d_j}, eq_t2i[j] = #{i != j : s_ij == d_j}.  IEEE comparisons (a NaN score is neither greater nor equal); a query whose own d is
+ * not finite gets gt = N - 1, eq = 0 (the worst rank).  Ranks are OPTIMISTIC: rank = 1 + gt, the (sim > diag).sum() form; eq counts the others tied
+ * with the query's own pair.  The N x N matrix is never written; rows, columns and k of the padding are masked by index.  The call zeroes its own
+ * outputs (they may be uninitialised), is asynchronous and deterministic (integer atomics only).
+ * ws: uia_retrieval_workspace_bytes(N, E) of scratch (the diagonal and the two normalised copies; 0 for a shape outside the limits). */
+size_t uia_retrieval_workspace_bytes(int N, int E);
+int uia_retrieval_ranks(void* stream, int N, int E, const float* img, const float* txt, int normalize, void* ws, size_t ws_bytes,
+                        int32_t* gt_i2t, int32_t* eq_i2t, int32_t* gt_t2i, int32_t* eq_t2i);
+/* Statistics of one retrieval direction.  gt int32 [N] on the device (uia_retrieval_ranks), k_values a HOST array of nk values, 1 <= nk <= 16, every
+ * K >= 1 (checked before any launch); 1 <= N <= 2^24.  With rank = 1 + gt, record fp64 [nk + 2] on the device: record[t] = 100 * #{rank <= K_t} / N
+ * (R@K), record[nk] the median rank (the two middle values averaged for even N, as numpy.median), record[nk + 1] the mean rank.  rsum is the sum of
+ * every R@K of both directions (two records).  Integer counting and selection, an exact integer rank sum; no float atomics.
+ * ws: uia_retrieval_stats_workspace_bytes(N) of scratch. */
+size_t uia_retrieval_stats_workspace_bytes(int N);
+int uia_retrieval_stats(void* stream, int N, const int32_t* gt, int nk, const int32_t* k_values, void* ws, size_t ws_bytes, double* record);
 
 /* ---------------------------------------------------------------------------------------------
  * Layout helpers around the GEMMs. */

@@ -227,6 +227,16 @@ int uia_surface_distances(void* stream, int B, int H, int W, const float* logits
     return uia_surface_launch((hipStream_t)stream, B, H, W, logits, label, percentile, ws, ws_bytes, hd, asd);
 }
 
+size_t uia_retrieval_workspace_bytes(int N, int E) { return uia_retrieval_ranks_ws_bytes(N, E); }
+int uia_retrieval_ranks(void* stream, int N, int E, const float* img, const float* txt, int normalize, void* ws, size_t ws_bytes,
+                        int32_t* gt_i2t, int32_t* eq_i2t, int32_t* gt_t2i, int32_t* eq_t2i) {
+    return uia_retrieval_ranks_launch((hipStream_t)stream, N, E, img, txt, normalize, ws, ws_bytes, gt_i2t, eq_i2t, gt_t2i, eq_t2i);
+}
+size_t uia_retrieval_stats_workspace_bytes(int N) { return uia_retrieval_stats_ws_bytes(N); }
+int uia_retrieval_stats(void* stream, int N, const int32_t* gt, int nk, const int32_t* k_values, void* ws, size_t ws_bytes, double* record) {
+    return uia_retrieval_stats_launch((hipStream_t)stream, N, gt, nk, k_values, ws, ws_bytes, record);
+}
+
 int uia_im2col_padded(void* stream, int dtype, int B, int C, int H, int W, int P, const float* img, void* cols, int64_t ldo) {
     return uia_im2col_padded_launch((hipStream_t)stream, dtype, B, C, H, W, P, img, cols, (long)ldo);
 }

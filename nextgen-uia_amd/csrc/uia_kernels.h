@@ -88,6 +88,11 @@ int uia_binary_cls_stats_launch(hipStream_t stream, int N, const float* p1, cons
 size_t uia_surface_ws_bytes(int B, int H, int W);
 int uia_surface_launch(hipStream_t stream, int B, int H, int W, const float* logits, const float* label, float percentile, void* ws, size_t ws_bytes,
                        double* hd, double* asd);
+size_t uia_retrieval_ranks_ws_bytes(int N, int E);
+int uia_retrieval_ranks_launch(hipStream_t stream, int N, int E, const float* img, const float* txt, int normalize, void* ws, size_t ws_bytes,
+                               int32_t* gt_i2t, int32_t* eq_i2t, int32_t* gt_t2i, int32_t* eq_t2i);
+size_t uia_retrieval_stats_ws_bytes(int N);
+int uia_retrieval_stats_launch(hipStream_t stream, int N, const int32_t* gt, int nk, const int32_t* k_values, void* ws, size_t ws_bytes, double* record);
 int uia_im2col_padded_launch(hipStream_t stream, int dtype, int B, int C, int H, int W, int P, const float* img, void* out, long ldo);
 int uia_embed_bwd_launch(hipStream_t stream, int rows, int D, int vocab, const int64_t* ids, const float* dx, float* dtable, long pad_id);
 int uia_embed_packed_launch(hipStream_t stream, int rows, int D, int vocab, int max_pos, const int64_t* ids, const int64_t* pos_idx, const float* table, const float* pos, const float* type0, float* out);

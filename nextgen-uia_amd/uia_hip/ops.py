@@ -1698,6 +1698,34 @@ def surface_distances(logits, label, percentile=95.0):
     return hd, asd
 
 
+def retrieval_ranks(img, txt, normalize=True):
+    """img, txt [N, E] paired features (non-fp32 is converted) -> (gt_i2t, eq_i2t, gt_t2i, eq_t2i), int32 device tensors [N]: for each query the number of
+    OTHER candidates scoring strictly above / exactly equal to its own pair, s_ij = <img_i, txt_j> on the exact fp32 MFMA (rows L2-normalised first when
+    `normalize`).  The N x N score matrix is never formed.  Enqueued only: nothing is read back."""
+    _p(img), _p(txt)                                              # CPU tensors are refused before anything else
+    assert img.dim() == 2 and img.shape == txt.shape and img.device == txt.device, f"retrieval_ranks: img {tuple(img.shape)} and txt {tuple(txt.shape)} must be paired [N, E]"
+    a, b = img.detach().float().contiguous(), txt.detach().float().contiguous()
+    N, E = a.shape
+    ws = torch.empty(lib().uia_retrieval_workspace_bytes(N, E), device=a.device, dtype=torch.uint8)
+    out = torch.empty(4, N, device=a.device, dtype=torch.int32)
+    check(lib().uia_retrieval_ranks(_stream(), N, E, _p(a), _p(b), 1 if normalize else 0, _p(ws), ws.numel(), _p(out[0]), _p(out[1]), _p(out[2]), _p(out[3])),
+          "uia_retrieval_ranks")
+    return out[0], out[1], out[2], out[3]
+
+
+def retrieval_stats(gt, k_values):
+    """gt int32 [N] (one direction of retrieval_ranks), k_values a sequence of K -> fp64 device record [len(k_values) + 2]: R@K in percent for each K, the
+    median and the mean of rank = 1 + gt."""
+    g = gt.reshape(-1).to(torch.int32).contiguous()
+    ks = (C.c_int32 * len(k_values))(*[int(k) for k in k_values])
+    N = g.numel()
+    pg = _p(g)
+    ws = torch.empty(lib().uia_retrieval_stats_workspace_bytes(N), device=g.device, dtype=torch.uint8)
+    rec = torch.empty(len(k_values) + 2, device=g.device, dtype=torch.float64)
+    check(lib().uia_retrieval_stats(_stream(), N, pg, len(k_values), ks, _p(ws), ws.numel(), _p(rec)), "uia_retrieval_stats")
+    return rec
+
+
 # ---------------------------------------------------------------- DINOv2 UNet decoder (csrc/unet_conv.hip, unet_bn.hip, unet_resample.hip)
 CONV3, CONVT_FWD, CONVT_BWD, CONV1 = 0, 1, 2, 3      # uia_conv_igemm / uia_conv_wgrad modes
 BN_SLICES = 256                            # UIA_BN_SLICES
