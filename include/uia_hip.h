@@ -237,6 +237,17 @@ int uia_attn_fwd_long(void* stream, int dtype, const uia_attn_desc* d);
  * bf16 and fp32, head dim 64, L <= 288, mask kind none only; every pointer 16-byte aligned, every leading dimension a whole number of 16-byte units. */
 int uia_attn_bwd_cls(void* stream, int dtype, const uia_attn_desc* d);
 
+/* The forward twin, for a caller that reads token 0 of the attention output and nothing else: the ONE query row q_0 of every (sequence, head) against
+ * the keys j < n, n = L (mask kind none, keylen null) or max(min(keylen[b], L), 1) (UIA_MASK_KEYPAD: the clamp uia_attn_fwd applies to an all-padding
+ * sequence).  s_j = scale·q_0·k_j, m = max_j s_j, P_j = exp(s_j − m), l = Σ_j P_j; out[b·ldo + h·64 + d] = Σ_j P_j v_j[d] / l — B compact rows, not
+ * B·L — and lse[b·H + h] = m + log l when lse is non-null.  q / k / v are addressed as in uia_attn_fwd (element (b,l,h,d) at ptr[(b·L+l)·ld_qkv + h·64 + d]);
+ * no K or V row at or beyond n is read.  The sums over the keys run in a fixed order: two launches on the same operands give the same bits.
+ * bf16 and fp32, head dim 64, L <= 288, row-major out (out_kb_rows = 0), no cu_seqlens; q / k / v / out 16-byte aligned, ld_qkv and ldo whole 16-byte units. */
+int uia_attn_fwd_cls(void* stream, int dtype, const uia_attn_desc* d);
+/* uia_attn_bwd_cls on what uia_attn_fwd_cls left: `out` is [B, H·64] (row b at out[b·ldo + h·64 + d], row-major) and `lse` is [B, H]; everything else
+ * — q / k / v, dout, the dense dq / dk / dv, row-major or K-blocked — as uia_attn_bwd_cls. */
+int uia_attn_bwd_cls_rows(void* stream, int dtype, const uia_attn_desc* d);
+
 /* ---------------------------------------------------------------------------------------------
  * LayerNorm over fp32 rows (model.py:163-169; timm / HF LayerNorm [third-party]).
  * x rows may be strided by ldx (elements); y / dy are compact [M,D].  Backward is for FROZEN
@@ -336,6 +347,11 @@ int uia_mona_spatial_bwd(void* stream, int dtype, const uia_mona_spatial_desc* d
  * adapter_conv parameters get no gradient from this token. */
 int uia_mona_cls_bwd(void* stream, int dtype, int B, int ntok, const void* dd, const void* t, int64_t ldt, void* dt, float p_drop, uint64_t seed,
                      const uint8_t* keep_mask);
+/* Its forward twin, the CLS token's share of uia_mona_spatial_fwd alone: d[b, c] = keep(b·ntok·64 + c) · gelu(t[b·ldt + c]) with compact d [B, 64] and t the
+ * CLS rows of project1's output, ldt elements apart (64 on a compact [B, 64] tensor).  ntok is the token count of the DENSE tensor the mask is indexed in
+ * (seed, or keep_mask uint8 [B, ntok, 64]): bit-identical to the CLS rows uia_mona_spatial_fwd writes for the same t, and uia_mona_cls_bwd with the
+ * same (ntok, p_drop, seed / keep_mask) regenerates the same mask. */
+int uia_mona_cls_fwd(void* stream, int dtype, int B, int ntok, const void* t, int64_t ldt, void* d, float p_drop, uint64_t seed, const uint8_t* keep_mask);
 
 /* The WHOLE adapter forward of mona.py:319-362 (and :96-151, :198-253, :427-487) in one launch, one workgroup per image:
  *     y = x + project2(drop(gelu(spatial(project1(LN(x)·gamma + x·gammax)))))
@@ -517,6 +533,10 @@ int uia_gather_rows(void* stream, int n, int D, const float* src, const int64_t*
 /* dst[r] = src[r·src_stride_bytes .. + row_bytes) for r < rows, dst compact: every stride-th row of a tensor of any element type (the CLS rows of a
  * saved activation).  row_bytes, src_stride_bytes and both pointers are whole 16-byte units. */
 int uia_copy_rows(void* stream, int rows, int64_t row_bytes, const void* src, int64_t src_stride_bytes, void* dst);
+/* dst[r·D + c] = the fp32 value of element (r·stride_rows, c) of a three-byte tensor, r < rows: float bits = (hi bits << 16) + (lo << 8).  hi: the bf16 plane,
+ * row-major (hi_kb_rows = 0, rows ldhi elements apart) or K-blocked with hi_kb_rows rows (element (row, c) at hi[((c/32)·hi_kb_rows + row)·32 + c%32], D a
+ * multiple of 32); lo: the int8 plane, row-major, rows ldlo apart.  The CLS rows of a residual stream that travels as three bytes per element. */
+int uia_rows3_to_f32(void* stream, int rows, int D, int64_t stride_rows, const void* hi, int64_t ldhi, int64_t hi_kb_rows, const int8_t* lo, int64_t ldlo, float* dst);
 /* dst = (accumulate ? dst : 0) + src*keep/(1-p), keep from the counter hash of (seed, index): LoRA input dropout
  * (src/adapters/lora.py:82-83) and its backward (same seed). */
 int uia_dropout(void* stream, int dtype, size_t n, const void* src, void* dst, float p, uint64_t seed, int accumulate);

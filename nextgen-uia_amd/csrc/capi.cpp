@@ -86,6 +86,20 @@ int uia_attn_bwd_cls(void* stream, int dtype, const uia_attn_desc* d) {
     NEED(d, "uia_attn_bwd_cls");
     return uia_attn_bwd_cls_launch((hipStream_t)stream, dtype, *d);
 }
+int uia_attn_bwd_cls_rows(void* stream, int dtype, const uia_attn_desc* d) {
+    NEED(d, "uia_attn_bwd_cls_rows");
+    return uia_attn_bwd_cls_launch((hipStream_t)stream, dtype, *d, true);
+}
+int uia_attn_fwd_cls(void* stream, int dtype, const uia_attn_desc* d) {
+    NEED(d, "uia_attn_fwd_cls");
+    return uia_attn_fwd_cls_launch((hipStream_t)stream, dtype, *d);
+}
+int uia_mona_cls_fwd(void* stream, int dtype, int B, int ntok, const void* t, int64_t ldt, void* d, float p_drop, uint64_t seed, const uint8_t* keep_mask) {
+    return uia_mona_cls_fwd_launch((hipStream_t)stream, dtype, B, ntok, t, (long)ldt, d, p_drop, seed, keep_mask);
+}
+int uia_rows3_to_f32(void* stream, int rows, int D, int64_t stride_rows, const void* hi, int64_t ldhi, int64_t hi_kb_rows, const int8_t* lo, int64_t ldlo, float* dst) {
+    return uia_rows3_to_f32_launch((hipStream_t)stream, rows, D, (long)stride_rows, hi, (long)ldhi, (long)hi_kb_rows, lo, (long)ldlo, dst);
+}
 int uia_mona_cls_bwd(void* stream, int dtype, int B, int ntok, const void* dd, const void* t, int64_t ldt, void* dt, float p_drop, uint64_t seed, const uint8_t* keep_mask) {
     return uia_mona_cls_bwd_launch((hipStream_t)stream, dtype, B, ntok, dd, t, (long)ldt, dt, p_drop, seed, keep_mask);
 }

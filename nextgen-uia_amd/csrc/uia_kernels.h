@@ -23,7 +23,10 @@ int uia_layernorm_bwd3_launch(hipStream_t stream, int dtype, int M, int D, long 
                               float* dx32, void* dxT, int8_t* dx_lo);
 int uia_layernorm_bwd_periodic_launch(hipStream_t stream, int dtype, int M, int D, const void* dy, const float* x, const void* x_hi, const int8_t* x_lo, long x_kb_rows,
                                       const float* gamma, float eps, const float* dres_rows, int period, float* dx32, void* dxT, int8_t* dx_lo);
-int uia_attn_bwd_cls_launch(hipStream_t stream, int dtype, const UiaAttnParams& p);
+int uia_attn_bwd_cls_launch(hipStream_t stream, int dtype, const UiaAttnParams& p, bool compact = false);      // compact: out [B, H*64] / lse [B, H] of uia_attn_fwd_cls
+int uia_attn_fwd_cls_launch(hipStream_t stream, int dtype, const UiaAttnParams& p);
+int uia_mona_cls_fwd_launch(hipStream_t stream, int dtype, int B, int ntok, const void* t, long ldt, void* d, float p_drop, uint64_t seed, const uint8_t* keep_mask);
+int uia_rows3_to_f32_launch(hipStream_t stream, int rows, int D, long stride_rows, const void* hi, long ldhi, long hi_kb_rows, const int8_t* lo, long ldlo, float* dst);
 int uia_mona_cls_bwd_launch(hipStream_t stream, int dtype, int B, int ntok, const void* dd, const void* t, long ldt, void* dt, float p_drop, uint64_t seed,
                             const uint8_t* keep_mask);
 int uia_copy_rows_launch(hipStream_t stream, int rows, long row_bytes, const void* src, long src_stride_bytes, void* dst);

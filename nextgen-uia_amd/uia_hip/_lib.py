@@ -195,6 +195,10 @@ PROTOTYPES = {
     "uia_copy_rows": (C.c_int, [vp, C.c_int, i64, vp, i64, vp]),
     "uia_attn_bwd_cls": (C.c_int, [vp, C.c_int, C.POINTER(AttnDesc)]),
     "uia_mona_cls_bwd": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, i64, vp, f32, C.c_uint64, vp]),
+    "uia_attn_fwd_cls": (C.c_int, [vp, C.c_int, C.POINTER(AttnDesc)]),
+    "uia_attn_bwd_cls_rows": (C.c_int, [vp, C.c_int, C.POINTER(AttnDesc)]),
+    "uia_mona_cls_fwd": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, i64, vp, f32, C.c_uint64, vp]),
+    "uia_rows3_to_f32": (C.c_int, [vp, C.c_int, C.c_int, i64, vp, i64, i64, vp, i64, vp]),
     "uia_layernorm_bwd_periodic": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, i64, vp, f32, vp, C.c_int, vp, vp, vp]),
 }
 

@@ -354,6 +354,17 @@ def _wait_inputs(stream, cur, ready):
         stream.wait_stream(cur)
 
 
+def _encode_image(model, images):
+    """encode_image for a consumer that reads the pooled features only: the tower's last layer may run on the CLS rows (UF.cls_only)."""
+    with UF.cls_only():
+        return model.encode_image(images)
+
+
+def _encode_text(model, ids):
+    with UF.cls_only():
+        return model.encode_text(ids)
+
+
 def contrastive_micro(model, criterion, images, ids, overlap_text=True, global_loss=False, streams=1, image_split=None, inputs_ready=False, ready=None, world=1,
                       loss_scale=1.0, features=None, opt=None):
     """Forward of both towers + InfoNCE + backward of ONE micro-batch: the gradients land in the trainable parameters' .grad (the flat optimiser's staging
@@ -383,8 +394,8 @@ def contrastive_micro(model, criterion, images, ids, overlap_text=True, global_l
         for s, st in enumerate(sts):
             st.wait_stream(cur)
             with torch.cuda.stream(st):
-                fis.append(model.encode_image(im[bounds[s]:bounds[s + 1]]))
-                fts.append(model.encode_text(tk[bounds[s]:bounds[s + 1]]))
+                fis.append(_encode_image(model, im[bounds[s]:bounds[s + 1]]))
+                fts.append(_encode_text(model, tk[bounds[s]:bounds[s + 1]]))
         for st, a, b in zip(sts, fis, fts):
             cur.wait_stream(st)
             a.record_stream(cur)
@@ -409,18 +420,18 @@ def contrastive_micro(model, criterion, images, ids, overlap_text=True, global_l
             for j, st in enumerate(tsides):
                 st.wait_stream(cur)
                 with torch.cuda.stream(st):
-                    fts.append(model.encode_text(tk[tb[j]:tb[j + 1]]))
+                    fts.append(_encode_text(model, tk[tb[j]:tb[j + 1]]))
         else:
             with torch.cuda.stream(side):
-                ft = model.encode_text(tk)
+                ft = _encode_text(model, tk)
         cuts = [0, image_split] + ([image_split + (mb - image_split) * j // (IMAGE_SLICES - 1) for j in range(1, IMAGE_SLICES - 1)] if IMAGE_SLICES > 2 else []) + [mb]
         extra = _mb_streams(images.device, len(cuts) - 2)
         parts = [None] * (len(cuts) - 1)
         for j, st in enumerate(extra):                       # slices 1.. on their own streams, slice 0 on the caller's
             st.wait_stream(cur)
             with torch.cuda.stream(st):
-                parts[j + 1] = model.encode_image(im[cuts[j + 1]:cuts[j + 2]])
-        parts[0] = model.encode_image(im[:cuts[1]])
+                parts[j + 1] = _encode_image(model, im[cuts[j + 1]:cuts[j + 2]])
+        parts[0] = _encode_image(model, im[:cuts[1]])
         for j, st in enumerate(extra):
             cur.wait_stream(st)
             parts[j + 1].record_stream(cur)
@@ -440,13 +451,13 @@ def contrastive_micro(model, criterion, images, ids, overlap_text=True, global_l
         elif ready is not None:
             side.wait_event(ready)
         with torch.cuda.stream(side):
-            ft = model.encode_text(tk)
-        fi = model.encode_image(im)
+            ft = _encode_text(model, tk)
+        fi = _encode_image(model, im)
         cur.wait_stream(side)
         ft.record_stream(cur)
     else:
-        fi = model.encode_image(im)
-        ft = model.encode_text(tk)
+        fi = _encode_image(model, im)
+        ft = _encode_text(model, tk)
     if features is not None:
         fi, ft = features(fi, ft)
     if global_loss:

@@ -26,7 +26,8 @@ from ._lib import UiaError
 # folded LayerNorm) and the rules for handing them out live in uia_hip.handoff; these are its names as the engine, the models and the tests use
 # them.  MonaFn and VitBlockFn call them through THIS module's globals (tests replace publish_grad3 / publish_fwd3 here to count calls).
 from .handoff import (ClsGrad, Resid3, _g3_partner_feeds, cls_grad_of, fwd3_of, grad3_decode, grad3_of, grad_resid3_enabled, hook_free, linear_chain,      # noqa: F401
-                      publish_cls_grad, publish_fwd3, publish_grad3, publish_rows, publish_t_copy, set_cls_grad, set_grad_resid3, t_copy_of, take_rows, zero_sums)
+                      publish_cls_grad, publish_fwd3, publish_grad3, publish_rows, publish_t_copy, set_cls_grad, set_grad_resid3, t_copy_of, take_rows, zero_sums,
+                      cls_only, set_cls_forward, take_cls_forward)
 from .handoff import clear as clear_t_copies      # noqa: F401
 
 _STATE = {"dtype": torch.bfloat16, "seed": 0x5EED, "calls": 0, "fwd_resid3": os.environ.get("UIA_FWD_RESID3", "1") != "0"}
@@ -434,6 +435,18 @@ def _as_act(buf, M, K, dt, n_consumer):
     return buf.as_rows() if ops.is_kb(buf) else buf
 
 
+def _rows_tile_cfg(m_dense, w, like, dt, **facts):
+    """Tile config for an M = B launch that stands in for rows of a dense launch of m_dense rows.  bf16: 0, the launcher's own choice for B rows.  fp32 is the
+    parity mode: the B rows run on the instantiation the dense launch would have run row 0 on (ops.plan_gemm of the dense shape), so every row's K chain is
+    accumulated in the dense launch's order and the row-wise stages reproduce the dense rows bit for bit given the same operands — what is left between the
+    CLS-only and the dense forward in fp32 is the attention kernel's own rounding.  (An existing instantiation either way; a few rows of a 256-row tile are idle.)"""
+    if dt != torch.float32 or not like.is_cuda:
+        return 0
+    N, K = (w.row if isinstance(w, ops.PackedW) else w).shape
+    plan = ops.plan_gemm(m_dense, N, K, 4, ops.num_cus(like.device.index), 0, packed=isinstance(w, ops.PackedW), **facts)
+    return next(L.base for L in plan if L.lo == 0)
+
+
 # ================================================================================================ Mona
 MONA_PARAM_ORDER = ("gamma", "gammax", "project1.weight", "project1.bias", "project2.weight", "project2.bias", "norm.weight", "norm.bias",
                     "adapter_conv.conv1.weight", "adapter_conv.conv1.bias", "adapter_conv.conv2.weight", "adapter_conv.conv2.bias",
@@ -455,15 +468,18 @@ class MonaFn(torch.autograd.Function):
         P = dict(zip(names, params))
         B, N, D = x.shape
         h, w = hw
-        assert N == 1 + h * w, f"Mona expects 1+h*w tokens, got N={N}, hw={hw}"
+        ntok = 1 + h * w
+        # the block in front ran on the CLS rows (CLS-only forward of a tower's last layer): x is [B, 1, D], the CLS rows of a [B, ntok, D] tensor nothing else of which is read
+        rows = N == 1 and ntok > 1 and handoff.take_cls_rows()
+        assert rows or N == ntok, f"Mona expects 1+h*w tokens, got N={N}, hw={hw}"
         dt = compute_dtype()
         x = x.contiguous()
         M = B * N
         bott = P["project1.weight"].shape[0]
         sp = {_SPATIAL_MAP[k]: v.detach().contiguous() for k, v in P.items() if k in _SPATIAL_MAP}
         seed = _next_seed() if (p_drop > 0 and keep_mask is None) else 0
-        fold = ln_fold_enabled(dt, M)          # the next block's first LayerNorm is folded into its QKV GEMM: leave it the T rows and their sums
-        if ops.mona_fused_ok(dt, D, h, w, bott):
+        fold = not rows and ln_fold_enabled(dt, M)          # the next block's first LayerNorm is folded into its QKV GEMM: leave it the T rows and their sums
+        if not rows and ops.mona_fused_ok(dt, D, h, w, bott):
             # the whole adapter in one launch (csrc/mona_fused.hip): u, t and d never travel through HBM between the stages
             train = any(ctx.needs_input_grad)
             u = _empty((M, D), dt, x) if train else None
@@ -485,16 +501,20 @@ class MonaFn(torch.autograd.Function):
                 ops.mona_pre_fwd(x, P["norm.weight"], P["norm.bias"], P["gamma"], P["gammax"], u, proj1=(w1.row if isinstance(w1, ops.PackedW) else w1, P["project1.bias"], t))
             else:
                 ops.mona_pre_fwd(x, P["norm.weight"], P["norm.bias"], P["gamma"], P["gammax"], u)
-                ops.gemm(u, w1, bias=P["project1.bias"], out_t=t)
+                ops.gemm(u, w1, bias=P["project1.bias"], out_t=t, tile_cfg=_rows_tile_cfg(B * ntok, w1, x, dt, out_t=True) if rows else 0)
             d = _empty((M, bott), dt, x)
-            ops.mona_spatial_fwd(variant, B, h, w, t, sp, d, p_drop=p_drop, seed=seed, keep_mask=keep_mask)
+            if rows:        # the CLS token bypasses the spatial operator: dropout · GELU of B rows, the mask indexed (and the seed drawn) as in the dense tensor
+                ops.mona_cls_fwd(B, ntok, t, d, p_drop=p_drop, seed=seed, keep_mask=keep_mask)
+            else:
+                ops.mona_spatial_fwd(variant, B, h, w, t, sp, d, p_drop=p_drop, seed=seed, keep_mask=keep_mask)
             w2 = WEIGHTS.get(P["project2.weight"], dt)
             y = torch.empty_like(x)
             y_t, sums = (_act(M, D, dt, x, 3 * D), zero_sums(M, x.device)) if fold else (None, None)      # read by the next block's QKV GEMM only
             # three: the next block takes the sum as a THREE-BYTE tensor: its hi plane is the T copy, one low byte per element beside it; no fp32 rows are written
             three = fold and dt == torch.bfloat16 and _STATE.get("fwd_resid3", True) and handoff.fwd3_consumer_ahead() and M > 2048 and x.is_cuda
             y_lo = torch.empty(M, D, device=x.device, dtype=torch.int8) if three else None
-            ops.gemm(d, w2, bias=P["project2.bias"], resid=x.view(M, D), out32=None if three else y.view(M, D), out_t=y_t, out_lo=y_lo, rowsum=sums)
+            ops.gemm(d, w2, bias=P["project2.bias"], resid=x.view(M, D), out32=None if three else y.view(M, D), out_t=y_t, out_lo=y_lo, rowsum=sums,
+                     tile_cfg=_rows_tile_cfg(B * ntok, w2, x, dt, out32=True, resid=True) if rows else 0)
             if three:
                 y = publish_fwd3(x.shape, x.device, y_t, y_lo, sums)
             elif fold:
@@ -506,13 +526,16 @@ class MonaFn(torch.autograd.Function):
         ctx.g3_out = dt == torch.bfloat16 and _g3_partner_feeds(x)
         # a CLS-sparse gradient (ClsGrad) is taken when the block in front takes one too: the whole tail of the tower then runs on the CLS rows
         front = handoff.partner_node(x)
-        ctx.cls_ok = u is not None and type(front).__name__ == "VitBlockFnBackward" and handoff.takes_cls_grad(x)
+        ctx.cls_ok = not rows and u is not None and type(front).__name__ == "VitBlockFnBackward" and handoff.takes_cls_grad(x)
+        ctx.rows_ntok = ntok if rows else 0      # > 0: x, u, t, d hold the B CLS rows; the backward is backward_cls on them
         return y
 
     @staticmethod
     def backward_cls(ctx, cg):
         """backward on a ClsGrad: the gradient is zero outside token 0 of every image and every stage but the spatial operator works row by row, so the same
-        sequence runs at M = B on the CLS rows of the saved x, u, t, d.  The CLS token bypasses the spatial operator: its parameters get exactly zero from here."""
+        sequence runs at M = B on the CLS rows of the saved x, u, t, d.  The CLS token bypasses the spatial operator: its parameters get exactly zero from here.
+        After a CLS-only forward (ctx.rows_ntok) the saved tensors ARE those rows, the mask index is the dense tensor's, and plain [B, 1, D] gradients go in and out."""
+        ntok = getattr(ctx, "rows_ntok", 0)
         variant, hw, p_drop, seed, names, has_mask = ctx.meta
         x, u, t, d, keep_mask, *params = ctx.saved_tensors
         keep_mask = keep_mask if has_mask else None
@@ -530,25 +553,33 @@ class MonaFn(torch.autograd.Function):
         dd = _empty((B, bott), dt, x)
         _wgrad_beside(side, lambda: ops.gemm(dy_t, w2t, out_t=dd), dy_t, cls_rows(d), G["project2.weight"], G["project2.bias"])
         dtt = _empty((B, bott), dt, x)
-        ops.mona_cls_bwd(B, N, dd, t, dtt, p_drop=p_drop, seed=seed, keep_mask=keep_mask)
+        ops.mona_cls_bwd(B, ntok or N, dd, t, dtt, p_drop=p_drop, seed=seed, keep_mask=keep_mask, t_rows=bool(ntok))
         w1t = WEIGHTS.get(P["project1.weight"], dt, transpose=True)
         fuse_du = x.is_cuda and ops.mona_pre_bwd_du_ok(B, D, bott, dt)
         du = None if fuse_du else _empty((B, D), dt, x)
         _wgrad_beside(side, None if fuse_du else (lambda: ops.gemm(dtt, w1t, out_t=du)), dtt, cls_rows(u), G["project1.weight"], G["project1.bias"])
         need_dx = ctx.needs_input_grad[0]
-        x_cls = ops.copy_rows(x.view(B * N, D), N, _empty((B, D), torch.float32, x))
+        x_cls = x.view(B, D) if ntok else ops.copy_rows(x.view(B * N, D), N, _empty((B, D), torch.float32, x))
         dx = _empty((B, D), torch.float32, x) if need_dx else None
         dx_t = _empty((B, D), dt, x) if (need_dx and dt != torch.float32) else None
         w1t_rows = (dtt, w1t.row if isinstance(w1t, ops.PackedW) else w1t) if fuse_du else None
         ops.mona_pre_bwd(du, x_cls, dy if need_dx else None, P["norm.weight"], P["norm.bias"], P["gamma"], P["gammax"], dx, dx_t,
                          G["gamma"], G["gammax"], G["norm.weight"], G["norm.bias"], dt_w1t=w1t_rows)
-        if need_dx:
+        if need_dx and ntok:
+            dx = dx.view(B, 1, D)
+            publish_t_copy(dx, dx_t.view(B, 1, D) if dx_t is not None else None)
+        elif need_dx:
             dx = publish_cls_grad(x.shape, x.device, dx, dx_t) if ctx.cls_ok else ClsGrad(dx, dx_t, N).decode()
         grads = tuple(None if direct else (G[k] if ctx.needs_input_grad[7 + i] else None) for i, k in enumerate(names))
         return (dx, None, None, None, None, None, None) + grads
 
     @staticmethod
     def backward(ctx, dy):
+        if getattr(ctx, "rows_ntok", 0):                     # CLS-only forward: dy is the plain [B, 1, D] gradient of the B rows
+            dy = dy.contiguous()
+            B, _, D = dy.shape
+            dt = ctx.saved_tensors[1].dtype
+            return MonaFn.backward_cls(ctx, ClsGrad(dy.view(B, D), t_copy_of(dy, dt).view(B, D) if dt != torch.float32 else None, ctx.rows_ntok))
         cg = cls_grad_of(dy)                                 # a CLS-sparse gradient from the head behind this adapter
         if cg is not None:
             return MonaFn.backward_cls(ctx, cg)
@@ -717,6 +748,10 @@ class VitBlockFn(torch.autograd.Function):
             h1 = _empty((M, D), dt, x)
             ops.layernorm_fwd(x2d, spec.ln1[0], spec.ln1[1], spec.eps, y_t=h1)
             ops.gemm(h1, WEIGHTS.get(spec.qkv[0], dt), bias=spec.qkv[1], out_t=qkv)
+        # the tower's head reads token 0 of THIS block's output and nothing else (handoff.cls_only, the last plain block of the loop): K and V of every token were
+        # needed, everything behind them is per query row — the rest of the block runs on the B CLS rows
+        if handoff.take_last_block_cls() and spec.mask is None and 1 < N <= ATTN_SINGLE_PASS_MAX and D == 64 * spec.heads and like.is_cuda:
+            return VitBlockFn._forward_cls(ctx, x, x3, qkv, spec, (B, N, D), dt, train)
         if N > ATTN_SINGLE_PASS_MAX:                         # long sequences (DINOv2 at 518 px: 1370 tokens): online-softmax forward, row-major output
             a = _empty((M, D), dt, like)
             ops.attn_fwd_long(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], a, B, spec.heads, N)
@@ -771,10 +806,51 @@ class VitBlockFn(torch.autograd.Function):
         return x2
 
     @staticmethod
+    def _forward_cls(ctx, x, x3, qkv, spec, shape, dt, train):
+        """The block behind its QKV GEMM on the B CLS rows: uia_attn_fwd_cls (one query row per head), the CLS rows of the block input gathered, then the projection
+        + residual, LayerNorm 2, fc1 and fc2 + residual at M = B through the ordinary launches (no LayerNorm fold below 2049 rows).  Returns [B, 1, D]; the backward
+        is backward_cls on the compact a, lse, x1, pre saved here."""
+        B, N, D = shape
+        like = qkv
+        a = _empty((B, D), dt, like)
+        lse = torch.empty(B, spec.heads, device=like.device, dtype=torch.float32) if train else None
+        ops.attn_fwd_cls(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], a, B, spec.heads, N, lse=lse)
+        x_cls = torch.empty(B, D, device=like.device, dtype=torch.float32)
+        if x3 is not None:
+            ops.rows3_to_f32(x3.hi, x3.lo, N, x_cls)
+        else:
+            ops.copy_rows(x.view(B * N, D), N, x_cls)
+        x1 = torch.empty(B, D, device=like.device, dtype=torch.float32)
+        M = B * N
+        wp = WEIGHTS.get(spec.proj[0], dt)
+        ops.gemm(a, wp, bias=spec.proj[1], resid=x_cls, out32=x1, tile_cfg=_rows_tile_cfg(M, wp, like, dt, out32=True, resid=True))
+        h2 = _empty((B, D), dt, like)
+        ops.layernorm_fwd(x1, spec.ln2[0], spec.ln2[1], spec.eps, y_t=h2)
+        F = spec.fc1[0].shape[0]
+        f = _empty((B, F), dt, like)
+        pre = _empty((B, F), dt, like) if train else None
+        w1, w2 = WEIGHTS.get(spec.fc1[0], dt), WEIGHTS.get(spec.fc2[0], dt)
+        ops.gemm(h2, w1, bias=spec.fc1[1], act=spec.act, aux_out=pre, out_t=f, tile_cfg=_rows_tile_cfg(M, w1, like, dt, act=True, aux_out=train, out_t=True))
+        x2 = torch.empty(B, 1, D, device=like.device, dtype=torch.float32)
+        ops.gemm(f, w2, bias=spec.fc2[1], resid=x1, out32=x2.view(B, D), tile_cfg=_rows_tile_cfg(M, w2, like, dt, out32=True, resid=True))
+        if train:
+            saved, ctx.layout = handoff.save_layout(x3.resid3 if x3 is not None else x, qkv, a, lse, x1, pre)
+            ctx.save_for_backward(*saved)
+            ctx.xshape = (B, N, D)
+            ctx.spec = spec
+            ctx.g3_out = dt == torch.bfloat16 and _g3_partner_feeds(x)
+            ctx.cls_ok = False          # the gradient of a [B, 1, D] output is an ordinary tensor: no ClsGrad token comes back
+            ctx.cls_fwd = True
+        handoff.cls_rows_out(True)
+        return x2
+
+    @staticmethod
     def backward_cls(ctx, cg):
         """backward on a ClsGrad: the MLP half, the LayerNorm-2 backward and the projection's data gradient work row by row and run at M = B on the CLS rows; the
         attention backward has one non-zero query row per head (ops.attn_bwd_cls) and makes the gradient dense; from the QKV data gradient on everything is the
-        dense backward, with dx1 — still CLS-sparse — entering the LayerNorm-1 backward as B rows (ops.layernorm_bwd_periodic)."""
+        dense backward, with dx1 — still CLS-sparse — entering the LayerNorm-1 backward as B rows (ops.layernorm_bwd_periodic).
+        After a CLS-only forward (ctx.cls_fwd) a, lse, x1 and pre hold the B rows already: nothing is gathered."""
+        compact = getattr(ctx, "cls_fwd", False)
         xin, qkv, a, lse, x1, pre = handoff.restore_layout(ctx.saved_tensors, ctx.layout)
         x3_in = isinstance(xin, Resid3)
         x = xin.lo if x3_in else xin
@@ -784,12 +860,12 @@ class VitBlockFn(torch.autograd.Function):
         F = pre.shape[1]
         dy = cg.rows32
         dy_t = dy if dt == torch.float32 else (cg.rows_t if cg.rows_t is not None else t_copy_of(dy, dt))
-        pre_cls = ops.copy_rows(pre, N, _empty((B, F), dt, x))
+        pre_cls = pre if compact else ops.copy_rows(pre, N, _empty((B, F), dt, x))
         dpre = _empty((B, F), dt, x)
         ops.gemm(dy_t, WEIGHTS.get(spec.fc2[0], dt, transpose=True), dact=spec.act, aux_in=pre_cls, out_t=dpre)
         dh = _empty((B, D), dt, x)
         ops.gemm(dpre, WEIGHTS.get(spec.fc1[0], dt, transpose=True), out_t=dh)
-        x1_cls = ops.copy_rows(x1, N, _empty((B, D), torch.float32, x))
+        x1_cls = x1 if compact else ops.copy_rows(x1, N, _empty((B, D), torch.float32, x))
         dx1 = _empty((B, D), torch.float32, x)
         dx1_t = _empty((B, D), dt, x) if dt != torch.float32 else dx1
         ops.layernorm_bwd(dh, x1_cls, spec.ln2[0], spec.eps, dres=dy, dx32=dx1, dx_t=dx1_t if dt != torch.float32 else None)
@@ -797,9 +873,9 @@ class VitBlockFn(torch.autograd.Function):
         ops.gemm(dx1_t, WEIGHTS.get(spec.proj[0], dt, transpose=True), out_t=da)
         dqkv = _attn_act(M, 3 * D, dt, x, D)                                          # read by the QKV dgrad GEMM only
         if ops.is_kb(dqkv):
-            ops.attn_bwd_cls(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], a, da, lse, dqkv, None, None, B, spec.heads, N)
+            ops.attn_bwd_cls(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], a, da, lse, dqkv, None, None, B, spec.heads, N, rows=compact)
         else:
-            ops.attn_bwd_cls(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], a, da, lse, dqkv[:, :D], dqkv[:, D:2 * D], dqkv[:, 2 * D:], B, spec.heads, N)
+            ops.attn_bwd_cls(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], a, da, lse, dqkv[:, :D], dqkv[:, D:2 * D], dqkv[:, 2 * D:], B, spec.heads, N, rows=compact)
         dh1 = _empty((M, D), dt, x)
         ops.gemm(dqkv, WEIGHTS.get(spec.qkv[0], dt, transpose=True), out_t=dh1)
         xrows = xin if x3_in else x.view(M, D)
@@ -819,6 +895,11 @@ class VitBlockFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dx2):
+        if getattr(ctx, "cls_fwd", False):                            # CLS-only forward: dx2 is the plain [B, 1, D] gradient of the B rows
+            dx2 = dx2.contiguous()
+            B, N, D = ctx.xshape
+            dt = ctx.saved_tensors[-1].dtype
+            return VitBlockFn.backward_cls(ctx, ClsGrad(dx2.view(B, D), t_copy_of(dx2, dt).view(B, D) if dt != torch.float32 else None, N))
         cg = cls_grad_of(dx2)                                         # a CLS-sparse gradient from the head or the adapter behind this block
         if cg is not None:
             if getattr(ctx, "cls_ok", False):
@@ -920,7 +1001,48 @@ def post_ln_embed(e32, ln, x_t):
     return _post_ln(e32, ln.weight, ln.bias, ln.eps, x_t)
 
 
-def post_ln_layer(res, x_t, L, B, heads, P, keylen, eps=1e-12, cu_seqlens=None, fold_sums=None, fold_out=False):
+def _res_cls_rows(res, L, B, D, eps):
+    """The fp32 residual an LnResidual stands for, on rows b·L only: [B, D].  Its three forms: the normalised rows themselves (stats None), a raw fp32 sum with
+    statistics (re-normalised here from the row: B rows), a three-byte raw sum (decoded by uia_rows3_to_f32, then normalised)."""
+    rows = torch.empty(B, D, device=res.w.device, dtype=torch.float32)
+    if res.lo is not None:
+        ops.rows3_to_f32(res.hi, res.lo, L, rows)
+    else:
+        ops.copy_rows(res.raw.view(-1, D), L, rows)
+        if res.stats is None:
+            return rows
+    ops.layernorm_fwd(rows, res.w, res.b, res.eps if res.eps is not None else eps, y32=rows)
+    return rows
+
+
+def post_ln_layer_cls_ok(x_t, heads, L, cu_seqlens=None):
+    """May the LAST layer of a post-LN tower run on the CLS rows (post_ln_layer(cls_only=True))?  Dense rows, 64-wide heads, within uia_attn_fwd_cls's length."""
+    D = x_t.cols if ops.is_kb(x_t) else x_t.shape[1]
+    return cu_seqlens is None and D == 64 * heads and 1 < L <= 288 and x_t.is_cuda and not (x_t.dtype != torch.float32 and _STATE.get("text_resid_t", False))
+
+
+def _post_ln_layer_cls(res, qkv, L, B, heads, P, keylen, eps, D, dt):
+    """The last layer behind its QKV GEMM when the head reads row b·L only: uia_attn_fwd_cls under the key-padding mask, the residual's CLS rows, then the output
+    projection + residual, LayerNorm, fc1 + GELU, fc2 + residual and LayerNorm at M = B through the ordinary launches.  Returns (LnResidual, x_t) of B rows."""
+    a = _empty((B, D), dt, qkv)
+    ops.attn_fwd_cls(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], a, B, heads, L, mask="keypad", keylen=keylen)
+    r = _res_cls_rows(res, L, B, D, eps)
+    s_a = torch.empty(B, D, device=qkv.device, dtype=torch.float32)
+    M = B * L
+    wo = WEIGHTS.get(P["attention.output.dense.weight"], dt)
+    ops.gemm(a, wo, bias=P["attention.output.dense.bias"], resid=r, out32=s_a, tile_cfg=_rows_tile_cfg(M, wo, qkv, dt, out32=True, resid=True))
+    h = _empty((B, D), dt, qkv)
+    ops.layernorm_fwd(s_a, P["attention.output.LayerNorm.weight"], P["attention.output.LayerNorm.bias"], eps, y_t=h, y32=s_a)
+    F = P["intermediate.dense.weight"].shape[0]
+    f = _empty((B, F), dt, qkv)
+    w1, w2 = WEIGHTS.get(P["intermediate.dense.weight"], dt), WEIGHTS.get(P["output.dense.weight"], dt)
+    ops.gemm(h, w1, bias=P["intermediate.dense.bias"], act="gelu", out_t=f, tile_cfg=_rows_tile_cfg(M, w1, qkv, dt, act=True, out_t=True))
+    ops.gemm(f, w2, bias=P["output.dense.bias"], resid=s_a, out32=r, tile_cfg=_rows_tile_cfg(M, w2, qkv, dt, out32=True, resid=True))
+    ops.layernorm_fwd(r, P["output.LayerNorm.weight"], P["output.LayerNorm.bias"], eps, y_t=h, y32=r)
+    return LnResidual(r, None, P["output.LayerNorm.weight"], P["output.LayerNorm.bias"]), h
+
+
+def post_ln_layer(res, x_t, L, B, heads, P, keylen, eps=1e-12, cu_seqlens=None, fold_sums=None, fold_out=False, cls_only=False):
     """HF BertLayer (post-LN), frozen: returns the new (deferred fp32 residual, T operand) pair.  P: dict of Parameters with the HF
     names relative to `encoder.layer.{i}.`; q/k/v weights are used as one fused [3D, D] matrix.  res: LnResidual.
     cu_seqlens: rows are PACKED valid tokens (un-padded captions); L is then the longest caption and no mask is needed.
@@ -942,6 +1064,8 @@ def post_ln_layer(res, x_t, L, B, heads, P, keylen, eps=1e-12, cu_seqlens=None, 
         ops.gemm(x_t, wq, bias=bq, out_t=qkv, lnfold=(res.stats, cq, D, res.eps))
     else:
         ops.gemm(x_t, P["_qkv_w"](dt), bias=P["_qkv_b"], out_t=qkv)
+    if cls_only:                                      # the caller reads row b·L of this layer's output and nothing else (post_ln_layer_cls_ok): B rows from here on
+        return _post_ln_layer_cls(res, qkv, L, B, heads, P, keylen, eps, D, dt)
     a = _attn_act(M, D, dt, x_t, D) if (D == 64 * heads and cu_seqlens is None) else _empty((M, D), dt, x_t)
     if cu_seqlens is not None:
         ops.attn_fwd(qkv[:, :D], qkv[:, D:2 * D], qkv[:, 2 * D:], a, B, heads, L, cu_seqlens=cu_seqlens)

@@ -6,6 +6,7 @@
   CLS-sparse gradient tokens       publish_cls_grad / cls_grad_of token address, pool of 64
   T rows + row sums (LN fold)      publish_rows / take_rows       raw stream, one slot
   zeroed row-sum arena             zero_sums                      raw stream, 48 slices
+  "token 0 is all I read"          cls_only / take_cls_forward    one flag per call, consumed by the tower's head (CLS-only forward of the last layer)
 
 with the rules that say when a token may be handed out (linear_chain, hook_free, _g3_partner_feeds, set_grad_resid3), the named type of a
 three-byte value (Resid3), of a CLS-sparse gradient (ClsGrad) and the one place that knows how a K-blocked activation goes through save_for_backward (save_layout / restore_layout).
@@ -17,7 +18,8 @@ import torch
 
 from . import ops
 
-_STATE = {"chain_depth": 0, "fwd3_next_plain": False, "grad_resid3": False, "cls_grad": True}
+_STATE = {"chain_depth": 0, "fwd3_next_plain": False, "grad_resid3": False, "cls_grad": True,
+          "cls_forward": True, "cls_decl": False, "cls_last": False, "cls_rows": False}
 
 
 # ------------------------------------------------------------------------------------------------ three-byte values
@@ -195,7 +197,14 @@ class linear_chain:
     def __exit__(self, *exc):
         _STATE["chain_depth"] -= 1
         _STATE["fwd3_next_plain"] = False
+        _STATE["cls_last"] = _STATE["cls_rows"] = False
         return False
+
+    @staticmethod
+    def last_block_cls(flag):
+        """The tower's loop says, before it runs a block, whether it is the LAST one, plain frozen and hook-free, under a head that reads token 0 only
+        (take_cls_forward): that block — and the adapter behind it — may then compute the B CLS rows of its output and nothing else."""
+        _STATE["cls_last"] = bool(flag)
 
     @staticmethod
     def next_is_plain_block(flag):
@@ -207,6 +216,54 @@ class linear_chain:
 def fwd3_consumer_ahead():
     """Inside a tower's own block loop, and the loop said that a plain frozen block comes next."""
     return _STATE["fwd3_next_plain"] and _STATE["chain_depth"] > 0
+
+
+def take_last_block_cls():
+    """True once, inside a tower's block loop whose head said that the last block may run on the CLS rows (consumed by that block's Function)."""
+    flag = _STATE["cls_last"] and _STATE["chain_depth"] > 0
+    _STATE["cls_last"] = False
+    return flag
+
+
+def cls_rows_out(flag):
+    """A block that ran on the CLS rows says so: its output is [B, 1, D], and the adapter behind it takes that as the CLS rows of a [B, 1 + h·w, D] tensor."""
+    _STATE["cls_rows"] = bool(flag)
+
+
+def take_cls_rows():
+    flag = _STATE["cls_rows"] and _STATE["chain_depth"] > 0
+    _STATE["cls_rows"] = False
+    return flag
+
+
+class cls_only:
+    """Per-call declaration of a tower's CALLER: "I read token 0 of this tower's output and nothing else" — what a contrastive step does with both towers.
+    The tower's head consumes it (take_cls_forward) on its way in, so a nested tower call of another consumer never sees it, and the scope's exit clears
+    it whether the call returned or raised.  Without it (a bare encode_image / encode_text, forward_features for a dense head) every layer runs dense."""
+
+    def __enter__(self):
+        _STATE["cls_decl"] = True
+        return self
+
+    def __exit__(self, *exc):
+        _STATE["cls_decl"] = False
+        return False
+
+
+def take_cls_forward():
+    """The declaration of cls_only(), consumed; False when the global switch set_cls_forward is off."""
+    flag = _STATE["cls_decl"] and _STATE["cls_forward"]
+    _STATE["cls_decl"] = False
+    return flag
+
+
+def cls_declared():
+    return _STATE["cls_decl"]
+
+
+def set_cls_forward(flag):
+    """Switch of the CLS-only forward of a tower's last layer (default on; off: the dense launches, for A/B).  It only ever applies under cls_only()."""
+    _STATE["cls_forward"] = bool(flag)
 
 
 def hook_free(*modules):

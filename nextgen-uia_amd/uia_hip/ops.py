@@ -944,10 +944,10 @@ def attn_bwd(q, k, v, out, dout, lse, dq, dk, dv, B, H, L, mask=None, keylen=Non
         check(lib().uia_attn_bwd(_stream(), _code(q.dtype), C.byref(d)), "uia_attn_bwd")
 
 
-def attn_bwd_cls(q, k, v, out, dout, lse, dq, dk, dv, B, H, L, mask=None, scale=None):
+def attn_bwd_cls(q, k, v, out, dout, lse, dq, dk, dv, B, H, L, mask=None, scale=None, rows=False):
     """uia_attn_bwd_cls: attention backward for a gradient that is zero outside token 0 of every sequence.  dout [B, H*64] holds the CLS rows only;
     q / k / v / out / lse / dq / dk / dv as attn_bwd (dq K-blocked: the fused gradient, dk = dv = None).  Every element of dq, dk, dv is written.
-    Head dim 64, no mask."""
+    Head dim 64, no mask.  rows: out [B, H*64] and lse [B, H] are the compact tensors attn_fwd_cls left (uia_attn_bwd_cls_rows)."""
     if mask not in (None, "none"):
         raise UiaError(f"attn_bwd_cls: mask {mask!r}: the CLS-query backward takes unmasked attention only")
     d = _attn_desc(q, k, v, out, lse, B, H, L, None, None, scale)
@@ -955,8 +955,11 @@ def attn_bwd_cls(q, k, v, out, dout, lse, dq, dk, dv, B, H, L, mask=None, scale=
         raise UiaError(f"attn_bwd_cls: head dim {d.dh}, only 64 is supported")
     if dout.dim() != 2 or dout.shape[0] != B or dout.shape[1] != H * 64 or dout.stride(1) != 1 or dout.dtype != q.dtype:
         raise UiaError(f"attn_bwd_cls: dout must be [{B}, {H * 64}] {q.dtype} rows (one per sequence), got {tuple(dout.shape)} {dout.dtype}")
-    if lse is None or lse.dtype != torch.float32 or not lse.is_contiguous() or lse.numel() != B * H * L:
-        raise UiaError(f"attn_bwd_cls: lse must be a contiguous fp32 [{B}, {H}, {L}] tensor")
+    compact = bool(rows)
+    if compact and (is_kb(out) or out.dim() != 2 or out.shape[0] != B or out.stride(1) != 1 or out.dtype != q.dtype):
+        raise UiaError(f"attn_bwd_cls(rows=True): out must be [{B}, {H * 64}] {q.dtype} rows (one per sequence)")
+    if lse is None or lse.dtype != torch.float32 or not lse.is_contiguous() or lse.numel() != (B * H if compact else B * H * L):
+        raise UiaError(f"attn_bwd_cls: lse must be a contiguous fp32 [{B}, {H}, {L}] tensor ([{B}, {H}] beside a compact out)")
     d.dout, d.lddo = _p(dout), dout.stride(0)
     if is_kb(dq):
         rows, cols, d.dqkv_kb_rows = _kb_dims(dq, "attention dqkv")
@@ -969,7 +972,47 @@ def attn_bwd_cls(q, k, v, out, dout, lse, dq, dk, dv, B, H, L, mask=None, scale=
             if t.dtype != q.dtype or t.dim() != 2 or t.shape[0] < B * L or t.shape[1] != H * 64 or t.stride(1) != 1 or t.stride(0) != dq.stride(0):
                 raise UiaError(f"attn_bwd_cls: {name} must be [{B * L}, {H * 64}] {q.dtype} rows sharing one row stride, got {tuple(t.shape)} {t.dtype}")
         d.dq, d.dk, d.dv, d.ld_dqkv = _p(dq), _p(dk), _p(dv), dq.stride(0)
-    check(lib().uia_attn_bwd_cls(_stream(), _code(q.dtype), C.byref(d)), "uia_attn_bwd_cls")
+    if compact:
+        check(lib().uia_attn_bwd_cls_rows(_stream(), _code(q.dtype), C.byref(d)), "uia_attn_bwd_cls_rows")
+    else:
+        check(lib().uia_attn_bwd_cls(_stream(), _code(q.dtype), C.byref(d)), "uia_attn_bwd_cls")
+
+
+def attn_fwd_cls(q, k, v, out, B, H, L, lse=None, mask=None, keylen=None, scale=None):
+    """uia_attn_fwd_cls: the attention output of token 0 of every sequence only.  q / k / v as attn_fwd (slices of the fused [B*L, 3*H*64] qkv);
+    out [B, H*64] row-major rows, lse fp32 [B, H] or None; mask None or "keypad" with keylen int32 [B].  Head dim 64, L <= 288."""
+    if mask not in (None, "none", "keypad"):
+        raise UiaError(f"attn_fwd_cls: mask {mask!r}: none or key padding only")
+    if is_kb(out) or out.dim() != 2 or out.shape[0] != B or out.shape[1] != H * 64 or out.stride(1) != 1 or out.dtype != q.dtype:
+        raise UiaError(f"attn_fwd_cls: out must be [{B}, {H * 64}] {q.dtype} rows (one per sequence)")
+    if q.shape[0] < B * L:
+        raise UiaError(f"attn_fwd_cls: q / k / v hold {q.shape[0]} rows, {B} sequences of {L} need {B * L}")
+    if lse is not None and (lse.dtype != torch.float32 or not lse.is_contiguous() or lse.numel() != B * H):
+        raise UiaError(f"attn_fwd_cls: lse must be a contiguous fp32 [{B}, {H}] tensor")
+    if mask == "keypad" and (keylen is None or keylen.dtype != torch.int32 or not keylen.is_contiguous() or keylen.numel() != B):
+        raise UiaError(f"attn_fwd_cls: key padding needs keylen int32 [{B}]")
+    d = _attn_desc(q, k, v, out, lse, B, H, L, mask, keylen if mask == "keypad" else None, scale)
+    if d.dh != 64:
+        raise UiaError(f"attn_fwd_cls: head dim {d.dh}, only 64 is supported")
+    check(lib().uia_attn_fwd_cls(_stream(), _code(q.dtype), C.byref(d)), "uia_attn_fwd_cls")
+
+
+def rows3_to_f32(hi, lo, stride_rows, dst):
+    """dst[r] = fp32 value of row r * stride_rows of the three-byte tensor (hi bf16 plane, row-major or KBlocked; lo int8 [M, D] row-major) (uia_rows3_to_f32)."""
+    rows, D = dst.shape
+    if dst.dtype != torch.float32 or not dst.is_contiguous() or lo.dtype != torch.int8 or lo.dim() != 2 or lo.stride(1) != 1 or lo.shape[1] != D:
+        raise UiaError(f"rows3_to_f32: dst fp32 contiguous [rows, D] and lo int8 [M, D] are required, got {tuple(dst.shape)} {dst.dtype} / {tuple(lo.shape)} {lo.dtype}")
+    _require(rows > 0 and stride_rows > 0 and (rows - 1) * stride_rows < lo.shape[0], f"rows3_to_f32: {rows} rows {stride_rows} apart do not fit the {lo.shape[0]} rows of lo")
+    if is_kb(hi):
+        hrows, hcols, kb_rows = _kb_dims(hi, "rows3_to_f32 hi")
+        _require(hi.dtype == torch.bfloat16 and hcols == D and (rows - 1) * stride_rows < hrows, "rows3_to_f32: the K-blocked hi plane must hold bf16 [M, D]")
+        hp, ldhi = hi.t.data_ptr(), D
+    else:
+        _require(hi.dtype == torch.bfloat16 and hi.dim() == 2 and hi.stride(1) == 1 and hi.shape[1] == D and (rows - 1) * stride_rows < hi.shape[0],
+                 "rows3_to_f32: the hi plane must hold bf16 [M, D] rows")
+        hp, ldhi, kb_rows = hi.data_ptr(), hi.stride(0), 0
+    check(lib().uia_rows3_to_f32(_stream(), rows, D, stride_rows, hp, ldhi, kb_rows, _p(lo), lo.stride(0), _p(dst)), "uia_rows3_to_f32")
+    return dst
 
 
 def layernorm_fwd(x, gamma, beta, eps, y_t=None, y32=None, rows=None, ldx=None, stats=None):
@@ -1357,14 +1400,24 @@ def mona_spatial_bwd(variant, B, h, w, t, params, dd, dt, grads, p_drop=0.0, see
     check(lib().uia_mona_spatial_bwd(_stream(), _code(t.dtype), C.byref(d)), "uia_mona_spatial_bwd")
 
 
-def mona_cls_bwd(B, ntok, dd, t, dt, p_drop=0.0, seed=0, keep_mask=None):
-    """The CLS token's share of mona_spatial_bwd (uia_mona_cls_bwd): dd, dt compact [B, 64]; t the forward's [B * ntok, 64] tensor, read at rows b * ntok;
-    the dropout mask (seed or keep_mask uint8 [B, ntok, 64]) is indexed as in the dense tensor.  No parameter gradients: the token bypasses the spatial operator."""
-    for name, x_, n in (("dd", dd, B * 64), ("dt", dt, B * 64), ("t", t, B * ntok * 64)):
+def mona_cls_fwd(B, ntok, t, d, p_drop=0.0, seed=0, keep_mask=None):
+    """The CLS token's share of mona_spatial_fwd (uia_mona_cls_fwd): t, d compact [B, 64]; the dropout mask (seed or keep_mask uint8 [B, ntok, 64]) is indexed
+    as in the dense tensor of ntok tokens per image."""
+    for name, x_ in (("t", t), ("d", d)):
+        _dense(x_, f"mona_cls_fwd: {name}", (t.dtype,), B * 64, align=2)
+    if keep_mask is not None:
+        _dense(keep_mask, "mona_cls_fwd: keep_mask", (torch.uint8,), B * ntok * 64)
+    check(lib().uia_mona_cls_fwd(_stream(), _code(t.dtype), B, ntok, _p(t), 64, _p(d), float(p_drop), int(seed) & 0xFFFFFFFFFFFFFFFF, _p(keep_mask)), "uia_mona_cls_fwd")
+
+
+def mona_cls_bwd(B, ntok, dd, t, dt, p_drop=0.0, seed=0, keep_mask=None, t_rows=False):
+    """The CLS token's share of mona_spatial_bwd (uia_mona_cls_bwd): dd, dt compact [B, 64]; t the forward's [B * ntok, 64] tensor, read at rows b * ntok
+    (t_rows: its B CLS rows alone, compact [B, 64], as mona_cls_fwd read them); the dropout mask (seed or keep_mask uint8 [B, ntok, 64]) is indexed as in the dense tensor.  No parameter gradients: the token bypasses the spatial operator."""
+    for name, x_, n in (("dd", dd, B * 64), ("dt", dt, B * 64), ("t", t, B * 64 if t_rows else B * ntok * 64)):
         _dense(x_, f"mona_cls_bwd: {name}", (t.dtype,), n, align=2)
     if keep_mask is not None:
         _dense(keep_mask, "mona_cls_bwd: keep_mask", (torch.uint8,), B * ntok * 64)
-    check(lib().uia_mona_cls_bwd(_stream(), _code(t.dtype), B, ntok, _p(dd), _p(t), ntok * 64, _p(dt), float(p_drop), int(seed) & 0xFFFFFFFFFFFFFFFF, _p(keep_mask)),
+    check(lib().uia_mona_cls_bwd(_stream(), _code(t.dtype), B, ntok, _p(dd), _p(t), 64 if t_rows else ntok * 64, _p(dt), float(p_drop), int(seed) & 0xFFFFFFFFFFFFFFFF, _p(keep_mask)),
           "uia_mona_cls_bwd")
 
 
