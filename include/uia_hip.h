@@ -487,6 +487,24 @@ int uia_retrieval_ranks(void* stream, int N, int E, const float* img, const floa
 size_t uia_retrieval_stats_workspace_bytes(int N);
 int uia_retrieval_stats(void* stream, int N, const int32_t* gt, int nk, const int32_t* k_values, void* ws, size_t ws_bytes, double* record);
 
+/* Training-time augmentation of a batch, one launch (the reference's src/datasets/{segmentation,classification}.py:14-156 on the device).  images fp32
+ * [B,1,S,S] in [0,1] (4-byte aligned; 16-byte accesses where an image starts on 16 bytes), masks uint8 [B,1,S,S] or NULL (then out_masks is NULL too),
+ * 1 <= B <= 65535, 8 <= S <= 1024.  programs: a HOST array int32 [B][14][4], every random decision already made: row 0 of an image is (n, with_mask,
+ * 0, 0) with 0 <= n <= 13 (only n is read; the sampler notes there whether it drew for a batch with masks), rows 1 .. n are (opcode, p0, p1, p2), float parameters as float32 bit patterns: 0 identity, 1 autocontrast, 2 equalize,
+ * 3 blur (p0 = sigma in [0.1, 2.5]), 4 contrast, 5 brightness, 6 sharpness (p0 = factor in [0, 4]), 7 posterize (p0 = bits, 1 .. 8), 8 solarize (p0 =
+ * threshold, 0 .. 256), 9 crop (p0, p1, p2 = top row i, left column j, side; resized to S x S), 10 horizontal flip, 11 vertical flip.  The whole table is
+ * checked before anything is enqueued (an unknown opcode, a parameter out of range, a crop leaving the image, n > 13: non-zero, nothing written); it is
+ * then copied to the workspace with hipMemcpyAsync on `stream`, so a pinned table must stay as it is until that copy has run.
+ * An image with n == 0 is copied bit for bit, and so is its mask.  Otherwise the image is quantised once to 8 bits (rint(255 x), clamped), run through
+ * its ops as PIL 12.2 runs them on an "L" image (integer / fp32 / fp64 arithmetic restated exactly; the crop is PIL's two-pass fixed-point bilinear
+ * resample) and written as q / 255; the mask bytes follow crop (PIL's nearest scaler) and flips.  The blur alone is this build's: the true separable
+ * Gaussian, taps to ceil(4 sigma), replicated edges, fp32 sums in tap order, rounded half up.  out_images / out_masks must not overlap the inputs.
+ * Asynchronous, deterministic (integer atomics only).  ws: uia_augment_workspace_bytes(B, S) of 16-byte aligned scratch (0 for a shape outside the
+ * limits): the device copy of the table, two byte planes and one fp32 plane per image, two byte planes per mask. */
+size_t uia_augment_workspace_bytes(int B, int S);
+int uia_augment_batch(void* stream, int B, int S, const float* images, const uint8_t* masks, const int32_t* programs, void* ws, size_t ws_bytes,
+                      float* out_images, uint8_t* out_masks);
+
 /* ---------------------------------------------------------------------------------------------
  * Layout helpers around the GEMMs. */
 int uia_cast(void* stream, int dtype, size_t n, const float* src, void* dst, float scale);          /* dst = T(scale*src) */

@@ -251,6 +251,12 @@ int uia_retrieval_stats(void* stream, int N, const int32_t* gt, int nk, const in
     return uia_retrieval_stats_launch((hipStream_t)stream, N, gt, nk, k_values, ws, ws_bytes, record);
 }
 
+size_t uia_augment_workspace_bytes(int B, int S) { return uia_augment_ws_bytes(B, S); }
+int uia_augment_batch(void* stream, int B, int S, const float* images, const uint8_t* masks, const int32_t* programs, void* ws, size_t ws_bytes,
+                      float* out_images, uint8_t* out_masks) {
+    return uia_augment_batch_launch((hipStream_t)stream, B, S, images, masks, programs, ws, ws_bytes, out_images, out_masks);
+}
+
 int uia_im2col_padded(void* stream, int dtype, int B, int C, int H, int W, int P, const float* img, void* cols, int64_t ldo) {
     return uia_im2col_padded_launch((hipStream_t)stream, dtype, B, C, H, W, P, img, cols, (long)ldo);
 }

@@ -96,6 +96,9 @@ int uia_retrieval_ranks_launch(hipStream_t stream, int N, int E, const float* im
                                int32_t* gt_i2t, int32_t* eq_i2t, int32_t* gt_t2i, int32_t* eq_t2i);
 size_t uia_retrieval_stats_ws_bytes(int N);
 int uia_retrieval_stats_launch(hipStream_t stream, int N, const int32_t* gt, int nk, const int32_t* k_values, void* ws, size_t ws_bytes, double* record);
+size_t uia_augment_ws_bytes(int B, int S);
+int uia_augment_batch_launch(hipStream_t stream, int B, int S, const float* images, const uint8_t* masks, const int32_t* programs, void* ws, size_t ws_bytes,
+                             float* out_images, uint8_t* out_masks);
 int uia_im2col_padded_launch(hipStream_t stream, int dtype, int B, int C, int H, int W, int P, const float* img, void* out, long ldo);
 int uia_embed_bwd_launch(hipStream_t stream, int rows, int D, int vocab, const int64_t* ids, const float* dx, float* dtable, long pad_id);
 int uia_embed_packed_launch(hipStream_t stream, int rows, int D, int vocab, int max_pos, const int64_t* ids, const int64_t* pos_idx, const float* table, const float* pos, const float* type0, float* out);

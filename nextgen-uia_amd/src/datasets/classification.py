@@ -2,8 +2,12 @@
 
 The reference reads grayscale PNGs listed in ../data/NextGen-UIA/classification/<dataset>/{train,val,test}.txt with labels from labels.csv, augments them
 with PIL / torchvision (:14-147) and hands batches of (image float32 [B, 3, S, S] in [0, 1] — ONE grayscale channel repeated, :183, :201-203 — label int64 [B],
-file names) to the loop, `shuffle=True, drop_last=True` for training and neither for validation / test (:232-262).  PIL / torchvision I/O and augmentation are
-host-side work outside the hot path (and absent from the build image); what the hot path needs is that batch contract and the three splits.
+file names) to the loop, `shuffle=True, drop_last=True` for training and neither for validation / test (:232-262).  PIL / torchvision I/O is host-side work
+outside the hot path (and absent from the build image); what the hot path needs is that batch contract and the three splits.  The augmentation (:14-151,
+`--strong_augs` / `--weak_augs`) is not done here: `__getitem__` returns the plain sample, and the training loop runs it on the device on the copied batch
+(src/datasets/augment.py: decisions on the host, pixels in one launch per batch; `--data_pt` batches only).  With a flag on (the default) a `--data_pt` file must hold SQUARE images of 8 to 1024 pixels a side
+(anything else is refused at the first training batch: resize the file or pass `--no-strong_augs --no-weak_augs`), and float images are taken to lie in
+[0, 1]: an augmented sample is quantised to 8 bits, which clamps values outside it, while an untouched sample of the same batch passes as it is.
 
 `--synthetic` supplies them deterministically by seed and balanced (even indices class 0, odd indices class 1): every image is U[0,1) texture scaled by 0.6;
 a class-1 image also carries a bright axis-aligned ellipse (the synthetic lesion of src/datasets/segmentation.py), so the classes are learnable.

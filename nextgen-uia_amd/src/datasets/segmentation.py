@@ -2,8 +2,12 @@
 
 The reference reads PNG pairs listed in ../data/NextGen-UIA/segmentation/<dataset>/{train,val,test}.txt with PIL, augments them with torchvision (:14-156) and
 hands batches of (image float32 [B, 3, S, S] in [0, 1] — ONE grayscale channel repeated three times, :175, :199-200 — label float32 [B, 1, S, S] in {0, 1},
-file names) to the loop, `shuffle=True, drop_last=True` for training and neither for validation / test (:223-251).  PIL / torchvision I/O and augmentation are
-host-side work outside the hot path (and absent from the build image); what the hot path needs is that batch contract and the three splits.  `--synthetic`
+file names) to the loop, `shuffle=True, drop_last=True` for training and neither for validation / test (:223-251).  PIL / torchvision I/O is host-side work
+outside the hot path (and absent from the build image); what the hot path needs is that batch contract and the three splits.  The augmentation (:14-156,
+`--strong_augs` / `--weak_augs`) is not done here: `__getitem__` returns the plain sample, and the training loops run it on the device on the copied batch
+(src/datasets/augment.py: decisions on the host, pixels in one launch per batch; `--data_pt` batches only).  With a flag on (the default) a `--data_pt` file must hold SQUARE images of 8 to 1024 pixels a side
+(anything else is refused at the first training batch: resize the file or pass `--no-strong_augs --no-weak_augs`), and float images are taken to lie in
+[0, 1]: an augmented sample is quantised to 8 bits, which clamps values outside it, while an untouched sample of the same batch passes as it is.  `--synthetic`
 supplies them deterministically (U[0,1) grayscale images with a random-ellipse mask); `--data_pt` takes real data as a .pt file of
 {"images": [N, 1 or 3, S, S] uint8 / float, "labels": [N, 1, S, S], optional "names", optional "split": {"train": idx, "val": idx, "test": idx}}.
 

@@ -8,7 +8,8 @@ the best-by-accuracy (strict >) checkpoint {"reduces", "blocks", "cls_head", "mo
 validation; `test()` (:287-365: checkpoint -> heads + Mona parameters by name -> metrics over the test split -> the Acc / Rec / Pre / F1 / AUC table,
 results.csv and the <time>_acc=XX.XX backup folder) and `main` (train unless --test, then ALWAYS test).
 Different on purpose: the iteration is engine.segmentation_step (zero_grad -> forward -> criterion -> backward -> AdamW, nothing read on the host) with the
-focal loss on the device (src/losses/focal.py); batches through engine.DevicePrefetcher; the metrics on the device (src/utils/cls_metrics.py, one host read
+focal loss on the device (src/losses/focal.py); batches through engine.DevicePrefetcher; --strong_augs / --weak_augs applied to --data_pt training batches on
+the device (src/datasets/augment.py); the metrics on the device (src/utils/cls_metrics.py, one host read
 per split).  ROC plots and TensorBoard figures are out of scope; scalars go to <train dir>/log/scalars.jsonl.  Data: `--synthetic` or `--data_pt`
 (src/datasets/classification.py).
 """
@@ -27,6 +28,7 @@ import torch
 
 from src.adapters import inject_lora_to_biomedclip, inject_mona_variant_to_open_clip
 from src.datasets import classification as dataset_cls
+from src.datasets.augment import stage_for
 from src.losses.focal import FocalLoss
 from src.models.biomedclip.zero_shot import load_adapter_by_name
 from src.third_party.biomedclip.model import create_biomedclip
@@ -159,11 +161,16 @@ def train(args, prepare=None):
     iter_num, best_val_acc, patience, logged, last = 0, 0.0, 0, [], None
     epoch_ms, val_hist = [], []
     cur = torch.cuda.current_stream()
+    augment = stage_for(args, with_mask=False)                   # --strong_augs / --weak_augs on --data_pt batches; None: bypassed
     for epoch in range(args.epochs):
         torch.cuda.synchronize()
         t0, n_it = time.perf_counter(), 0
+        if augment is not None:
+            augment.set_epoch(epoch)
         for images, labels, ready in train_pf:
             cur.wait_event(ready)
+            if augment is not None:
+                images, _ = augment(images)
             loss, _ = segmentation_step(model, criterion, opt, images.float(), labels, lr=cosine_lr(args.lr, args.lr_min, iter_num, max_iters))
             if iter_num % 10 == 0:
                 logged.append((iter_num, loss))
@@ -206,7 +213,8 @@ def train(args, prepare=None):
     if not os.path.exists(os.path.join(args.train_snapshot_path, "best_model.pth")):
         logging.warning("no validation improved on an accuracy of 0.0: saving the last iterate as best_model.pth (the reference has no checkpoint then and fails in test())")
         torch.save(checkpoint_dict(model), os.path.join(args.train_snapshot_path, "best_model.pth"))
-    out = {"iters": iter_num, "best_val_acc": best_val_acc, "last_loss": last, "val": val_hist, "epochs": epoch_ms}
+    out = {"iters": iter_num, "best_val_acc": best_val_acc, "last_loss": last, "val": val_hist, "epochs": epoch_ms,
+           "augmented_images": augment.augmented if augment is not None else 0}
     if args.stats_json:
         import json
         with open(args.stats_json, "w") as f:

@@ -9,7 +9,8 @@ per-iteration cosine schedule, validation by mean foreground Dice every 10 epoch
 the test pass after every validation (:259-280), `test()` (:283-355: checkpoint -> heads + Mona parameters by name -> metrics over the test split -> the
 Metric / Mean / Std table, results.csv and the backup folder) and `main` (train unless --test, then ALWAYS test).
 Different on purpose: the iteration is engine.segmentation_step with nothing read on the host, batches through engine.DevicePrefetcher (one grayscale channel +
-a uint8 mask per image, repeated on the device), Dice / IoU on the device; MONAI's HD95 / ASD (scipy surface distances on the host) are reported as NaN and
+a uint8 mask per image, repeated on the device), --strong_augs / --weak_augs applied to --data_pt training batches on the device (src/datasets/augment.py),
+Dice / IoU on the device; MONAI's HD95 / ASD (scipy surface distances on the host) are reported as NaN and
 TensorBoard scalars go to <train dir>/log/scalars.jsonl.  Data: `--synthetic` or `--data_pt` (src/datasets/segmentation.py).
 """
 import argparse
@@ -29,6 +30,7 @@ from src.adapters import inject_lora_to_biomedclip, inject_mona_variant_to_open_
 from src.losses.dice import DiceCELoss
 from src.models.biomedclip.zero_shot import load_adapter_by_name
 from src.datasets import segmentation as dataset_seg
+from src.datasets.augment import stage_for
 from src.datasets.segmentation import as_model_input
 from src.third_party.biomedclip.model import create_biomedclip
 from src.third_party.timm.clip_adapter import TimmCLIPAdapter
@@ -150,13 +152,18 @@ def train(args, prepare=None):
     epoch_ms = []
     cur = torch.cuda.current_stream()
     bufs = {}                                                    # the widened training batch lives in the same two tensors every iteration
+    augment = stage_for(args, with_mask=True, rank=rank)         # --strong_augs / --weak_augs on --data_pt batches; None: bypassed
     dm.set_epoch(0)
     batches = iter(train_pf)
     for epoch in range(args.epochs):
         torch.cuda.synchronize()
         t0, n_it = time.perf_counter(), 0
+        if augment is not None:
+            augment.set_epoch(epoch)
         for images, labels, ready in batches:
             cur.wait_event(ready)
+            if augment is not None:
+                images, labels = augment(images, labels)
             images, labels = as_model_input(images, labels, args.in_channels, bufs, widen=False)
             loss, _ = segmentation_step(model, criterion, opt, images, labels, lr=cosine_lr(args.lr, args.lr_min, iter_num, max_iters))
             if iter_num % 10 == 0:
@@ -213,7 +220,8 @@ def train(args, prepare=None):
     if rank == 0 and not os.path.exists(os.path.join(args.train_snapshot_path, "best_model.pth")):
         logging.warning("no validation improved on a mean Dice of 0.0: saving the last iterate as best_model.pth (the reference has no checkpoint then and fails in test())")
         torch.save(checkpoint_dict(model), os.path.join(args.train_snapshot_path, "best_model.pth"))
-    out = {"iters": iter_num, "best_val_dice": best_val_dice, "last_loss": last, "rank": rank, "world": world, "epochs": epoch_ms}
+    out = {"iters": iter_num, "best_val_dice": best_val_dice, "last_loss": last, "rank": rank, "world": world, "epochs": epoch_ms,
+           "augmented_images": augment.augmented if augment is not None else 0}
     if args.stats_json and rank == 0:
         import json
         with open(args.stats_json, "w") as f:

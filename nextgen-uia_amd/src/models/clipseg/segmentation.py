@@ -17,8 +17,8 @@ Kept, by reference line:
 Different on purpose: the iteration is engine.segmentation_step — the step `bench.py --config clipseg` times — and nothing is read on the host per iteration
 (the reference's loss.item() every tenth iteration goes to a log of device scalars that is flushed at validation time); batches arrive through
 engine.DevicePrefetcher (loader workers -> shared-memory ring -> copy stream), one grayscale channel + a uint8 mask per image, repeated to three channels on the
-device; validation metrics are computed on the device (Dice / IoU, MONAI semantics; HD95 / ASD are host-side scipy work and are reported as NaN); TensorBoard
-scalars go to <train dir>/log/scalars.jsonl.  Data: --synthetic or --data_pt (src/datasets/segmentation.py).  Build-only flags are listed after the
+device; --strong_augs / --weak_augs act on --data_pt training batches there too (src/datasets/augment.py, one launch per batch); validation metrics are
+computed on the device (Dice / IoU, MONAI semantics; HD95 / ASD are host-side scipy work and are reported as NaN); TensorBoard scalars go to <train dir>/log/scalars.jsonl.  Data: --synthetic or --data_pt (src/datasets/segmentation.py).  Build-only flags are listed after the
 reference's in get_args.  Data parallel under torch.distributed.run: every rank trains on its shard, ONE all-reduce of the decoder gradients per iteration.
 """
 import argparse
@@ -35,6 +35,7 @@ import numpy as np
 import torch
 
 from src.datasets import segmentation as dataset_seg
+from src.datasets.augment import stage_for
 from src.datasets.segmentation import as_model_input, synthetic_batch      # noqa: F401  (synthetic_batch: bench.py and tools import it from here)
 from src.losses.dice import DiceCELoss
 from src.models.clipseg.prompt import busi_prompt, ln_prompt, prostate_prompt, thyroid_prompt
@@ -54,7 +55,7 @@ def get_args(argv=None):
     parser.add_argument("--img_size", type=int, default=224, help="Image width and height")
     parser.add_argument("--patch_size", type=int, default=16, help="Patch size")
     parser.add_argument("--num_workers", type=int, default=8)
-    # Augmentation related (accepted; augmentation belongs to the reference's PIL loaders)
+    # Augmentation related (applied to --data_pt training batches on the device: src/datasets/augment.py)
     parser.add_argument("--strong_augs", default=True, action=argparse.BooleanOptionalAction, help="Use strong augs")
     parser.add_argument("--weak_augs", default=True, action=argparse.BooleanOptionalAction, help="Use weak augs")
     # Model related
@@ -196,6 +197,7 @@ def train(args):
     epoch_ms, logged = [], []
     cur = torch.cuda.current_stream()
     bufs = {}                                                    # the widened training batch lives in the same two tensors every iteration
+    augment = stage_for(args, with_mask=True, rank=rank)         # --strong_augs / --weak_augs on --data_pt batches; None: bypassed
     dm.set_epoch(0)
     batches = iter(train_pf)
     ab = os.environ.get("UIA_SEG_AB", "")                     # measurement knobs (tools/ab_clipseg_entry.sh); none is set in normal use
@@ -213,6 +215,8 @@ def train(args):
         torch.cuda.synchronize()
         t0, w0, enq = time.perf_counter(), train_pf.wait_s, 0.0
         n_it = 0
+        if augment is not None:
+            augment.set_epoch(epoch)
         if "resident" in ab and epoch > 0:                      # the same device batch every iteration, the prefetcher idle: the loop's floor
             if epoch == 1:
                 first = next(iter(train_pf))
@@ -221,6 +225,8 @@ def train(args):
         for images, labels, ready in batches:
             t1 = time.perf_counter()
             cur.wait_event(ready)
+            if augment is not None:
+                images, labels = augment(images, labels)
             images, labels = as_model_input(images, labels, args.in_channels, bufs, widen=False)
             # scheduler.step() follows optimizer.step() (:147-148): iteration i runs at the closed form's value for i
             loss, _ = segmentation_step(model, criterion, opt, images, labels, input_ids=_batch_prompt(prompt, cache, images.shape[0]),
@@ -304,7 +310,8 @@ def train(args):
         # no validation ever beat a mean Dice of 0.0: the reference has no checkpoint then and fails in test() on the missing file.  Keep the last iterate instead.
         logging.warning("no validation improved on a mean Dice of 0.0: saving the last iterate as best_model.pth")
         torch.save({"decoder": model.decoder.state_dict()}, os.path.join(args.train_snapshot_path, "best_model.pth"))
-    out = {"iters": iter_num, "best_val_dice": best_val_dice, "rank": rank, "world": world, "epochs": epoch_ms}
+    out = {"iters": iter_num, "best_val_dice": best_val_dice, "rank": rank, "world": world, "epochs": epoch_ms,
+           "augmented_images": augment.augmented if augment is not None else 0}
     if sampler is not None:
         out["power"] = sampler.stop()
     if measure is not None:

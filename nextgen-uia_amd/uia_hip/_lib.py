@@ -159,6 +159,8 @@ PROTOTYPES = {
     "uia_retrieval_ranks": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, C.c_int, vp, sz, vp, vp, vp, vp]),
     "uia_retrieval_stats_workspace_bytes": (sz, [C.c_int]),
     "uia_retrieval_stats": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, vp, sz, vp]),
+    "uia_augment_workspace_bytes": (sz, [C.c_int, C.c_int]),
+    "uia_augment_batch": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp, vp, sz, vp, vp]),
     "uia_infonce_workspace_bytes": (sz, [C.c_int, C.c_int]),
     "uia_infonce_fwd_bwd": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, f32, f32, vp, vp, vp, vp, sz]),
     "uia_adamw_clip_step": (C.c_int, [vp, sz, vp, vp, vp, vp, f32, f32, f32, f32, f32, f32, C.c_int, f32, vp]),

@@ -1779,6 +1779,48 @@ def retrieval_stats(gt, k_values):
     return rec
 
 
+# ---------------------------------------------------------------- training-time augmentation (csrc/augment.hip)
+AUG_MAX_OPS, AUG_ROWS = 13, 14             # ops per image; rows of an image in the program table (row 0: n, with_mask, 0, 0)
+
+
+def augment_workspace(B, S, device):
+    """The scratch of one uia_augment_batch call on [B, 1, S, S] (a caller that augments every batch keeps it)."""
+    need = lib().uia_augment_workspace_bytes(int(B), int(S))
+    if need == 0:
+        raise UiaError(f"augment_batch: shape B={B} S={S} is outside the kernel's limits (1 <= B <= 65535, 8 <= S <= 1024)")
+    return torch.empty(need, device=device, dtype=torch.uint8)
+
+
+def augment_batch(images, masks, programs, out_images=None, out_masks=None, ws=None):
+    """images fp32 [B, 1, S, S] in [0, 1] and masks uint8 [B, 1, S, S] (or None) on the device, programs a HOST int32 tensor [B, 14, 4]
+    (src/datasets/augment.draw_programs; pinned memory makes its copy asynchronous, and it must then stay unchanged until the copy has run) ->
+    (out_images, out_masks): every image run through its program in one launch; an image with an empty program is copied bit for bit.
+    Enqueued only: nothing is read back.  out_* and ws may be handed in to be reused."""
+    _p(images), _p(masks)                                         # CPU tensors are refused before anything else
+    if images.dim() != 4 or images.shape[1] != 1 or images.shape[2] != images.shape[3] or images.dtype != torch.float32 or not images.is_contiguous():
+        raise UiaError(f"augment_batch: images must be contiguous fp32 [B, 1, S, S], got {images.dtype} {tuple(images.shape)}")
+    B, _, S, _ = images.shape
+    if masks is not None and (masks.shape != images.shape or masks.dtype != torch.uint8 or not masks.is_contiguous() or masks.device != images.device):
+        raise UiaError(f"augment_batch: masks must be contiguous uint8 {tuple(images.shape)} beside the images, got {masks.dtype} {tuple(masks.shape)}")
+    if (not isinstance(programs, torch.Tensor) or programs.is_cuda or programs.dtype != torch.int32 or tuple(programs.shape) != (B, AUG_ROWS, 4)
+            or not programs.is_contiguous()):
+        raise UiaError(f"augment_batch: programs must be a contiguous host int32 tensor [{B}, {AUG_ROWS}, 4]")
+    if out_images is None:
+        out_images = torch.empty_like(images)
+    if masks is not None and out_masks is None:
+        out_masks = torch.empty_like(masks)
+    if masks is None:
+        out_masks = None
+    for o, i, name in ((out_images, images, "out_images"), (out_masks, masks, "out_masks")):
+        if i is not None and (o.shape != i.shape or o.dtype != i.dtype or not o.is_contiguous() or o.device != i.device):
+            raise UiaError(f"augment_batch: {name} must match its input ({i.dtype} {tuple(i.shape)}, contiguous, same device)")
+    if ws is None:
+        ws = augment_workspace(B, S, images.device)
+    check(lib().uia_augment_batch(_stream(), B, S, _p(images), _p(masks), programs.data_ptr(), _p(ws), ws.numel(), _p(out_images), _p(out_masks)),
+          "uia_augment_batch")
+    return out_images, out_masks
+
+
 # ---------------------------------------------------------------- DINOv2 UNet decoder (csrc/unet_conv.hip, unet_bn.hip, unet_resample.hip)
 CONV3, CONVT_FWD, CONVT_BWD, CONV1 = 0, 1, 2, 3      # uia_conv_igemm / uia_conv_wgrad modes
 BN_SLICES = 256                            # UIA_BN_SLICES
