@@ -486,6 +486,25 @@ int uia_retrieval_ranks(void* stream, int N, int E, const float* img, const floa
  * ws: uia_retrieval_stats_workspace_bytes(N) of scratch. */
 size_t uia_retrieval_stats_workspace_bytes(int N);
 int uia_retrieval_stats(void* stream, int N, const int32_t* gt, int nk, const int32_t* k_values, void* ws, size_t ws_bytes, double* record);
+/* Top-K listing: each query's K best gallery rows, from the score tiles of uia_retrieval_ranks with a selection epilogue; the Q x N matrix is never
+ * written.  queries fp32 [Q,E], gallery fp32 [N,E], row-major contiguous, 16-byte aligned; 1 <= Q, N <= 2^24, E % 4 == 0, 4 <= E <= 4096,
+ * 1 <= K <= min(N, 32).  Scores s_qj = <a_q, b_j> with the rows divided by max(||row||, 1e-12) when normalize != 0: the same k-ordered fmaf chain and the
+ * same stored normalised rows as uia_retrieval_ranks, so the same bits for the same two rows, whatever tile, lane, split or shape holds them (the paired
+ * i2t listing is (img, txt), the t2i listing (txt, img): a product commutes bit for bit).
+ * Row q of the outputs is the first K candidates under ONE total order: score descending by IEEE comparison (+0 == -0), equal scores by gallery index
+ * ascending; a NaN score ranks below every non-NaN score, NaN scores among themselves by index ascending (a NaN query row lists 0 .. K-1 with NaN
+ * scores; a NaN gallery row appears only when fewer than K others exist).  idx int32 [Q][K]: idx[q][r] is the gallery index of place r + 1;
+ * score fp32 [Q][K] its s_qj.  Padding rows, columns and k are masked by index: a zero-padded column is never selectable.
+ * splits: the number of gallery strips a row tile's work is cut into (grid = row tiles x splits, partial lists merged per row by a second kernel);
+ * 0 takes uia_retrieval_topk_splits(Q, N), a pure host function (512 blocks aimed at, at most one strip per 128 gallery rows, 1 once the row tiles
+ * alone fill the device); 1 .. 512 otherwise, and a value above the rule's is held to it.  The order is total, so the result does not depend on splits.
+ * Everything is checked before anything is enqueued (non-zero, uia_last_error(), nothing written).  Asynchronous, deterministic (no atomics); writes
+ * every element of idx and score.  ws: uia_retrieval_topk_workspace_bytes(Q, N, E, K) of scratch (the two normalised copies and the partial lists,
+ * at most 512 x 128 x K entries; 0 for a shape outside the limits). */
+size_t uia_retrieval_topk_workspace_bytes(int Q, int N, int E, int K);
+int uia_retrieval_topk_splits(int Q, int N);
+int uia_retrieval_topk(void* stream, int Q, int N, int E, int K, const float* queries, const float* gallery, int normalize, int splits, void* ws,
+                       size_t ws_bytes, int32_t* idx, float* score);
 
 /* Training-time augmentation of a batch, one launch (the reference's src/datasets/{segmentation,classification}.py:14-156 on the device).  images fp32
  * [B,1,S,S] in [0,1] (4-byte aligned; 16-byte accesses where an image starts on 16 bytes), masks uint8 [B,1,S,S] or NULL (then out_masks is NULL too),

@@ -250,6 +250,12 @@ size_t uia_retrieval_stats_workspace_bytes(int N) { return uia_retrieval_stats_w
 int uia_retrieval_stats(void* stream, int N, const int32_t* gt, int nk, const int32_t* k_values, void* ws, size_t ws_bytes, double* record) {
     return uia_retrieval_stats_launch((hipStream_t)stream, N, gt, nk, k_values, ws, ws_bytes, record);
 }
+size_t uia_retrieval_topk_workspace_bytes(int Q, int N, int E, int K) { return uia_retrieval_topk_ws_bytes(Q, N, E, K); }
+int uia_retrieval_topk_splits(int Q, int N) { return uia_retrieval_topk_rule(Q, N); }
+int uia_retrieval_topk(void* stream, int Q, int N, int E, int K, const float* queries, const float* gallery, int normalize, int splits, void* ws,
+                       size_t ws_bytes, int32_t* idx, float* score) {
+    return uia_retrieval_topk_launch((hipStream_t)stream, Q, N, E, K, queries, gallery, normalize, splits, ws, ws_bytes, idx, score);
+}
 
 size_t uia_augment_workspace_bytes(int B, int S) { return uia_augment_ws_bytes(B, S); }
 int uia_augment_batch(void* stream, int B, int S, const float* images, const uint8_t* masks, const int32_t* programs, void* ws, size_t ws_bytes,

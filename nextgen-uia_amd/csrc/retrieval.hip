@@ -10,6 +10,8 @@
 //     query's own pair.  IEEE comparisons: a NaN score is neither greater nor equal; a query whose own d is not finite gets gt = N - 1, eq = 0.
 //   * uia_retrieval_stats: R@K (100 · #{rank <= K} / N), the median rank (numpy.median: the two middle values averaged for even N) and the mean rank of
 //     one direction's gt, as an fp64 record on the device.  rsum, the sum of every R@K of both directions, is formed by the caller from two records.
+//   * uia_retrieval_topk: each query's K <= 32 best gallery rows (queries [Q, E] against gallery [N, E], rectangular), from the same score tiles with a
+//     selection epilogue instead of the counts; one total order (score descending, equal scores by index ascending, NaN last).  See "top-K listing" below.
 //
 // Position independence (the contract of the rank counts): the bits of s_ij depend only on the values of row i of img and row j of txt.
 //   - v_mfma_f32_32x32x2_f32 is bit for bit a k-ordered fmaf chain from C = 0 (one rounding per product, no wider accumulator), and every element of every
@@ -55,14 +57,14 @@ RankLayout rank_layout(int N, int E) {
     return l;
 }
 
-// One wave per row: dst = src / max(||src||, 1e-12) (F.normalize; the eps of infonce.hip).  Rows 0 .. N-1 are img, N .. 2N-1 txt.
-__global__ __launch_bounds__(256) void rt_normalize_kernel(int N, int E, const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ an,
-                                                            float* __restrict__ bn) {
+// One wave per row: dst = src / max(||src||, 1e-12) (F.normalize; the eps of infonce.hip).  Rows 0 .. NA-1 are a's, NA .. NA+NB-1 b's.
+__global__ __launch_bounds__(256) void rt_normalize_kernel(int NA, int NB, int E, const float* __restrict__ a, const float* __restrict__ b,
+                                                            float* __restrict__ an, float* __restrict__ bn) {
     const size_t row = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     const int lane = threadIdx.x & 63;
-    if (row >= 2 * (size_t)N) return;
-    const float* src = row < (size_t)N ? a + row * E : b + (row - N) * E;
-    float* dst = row < (size_t)N ? an + row * E : bn + (row - N) * E;
+    if (row >= (size_t)NA + (size_t)NB) return;
+    const float* src = row < (size_t)NA ? a + row * E : b + (row - NA) * E;
+    float* dst = row < (size_t)NA ? an + row * E : bn + (row - NA) * E;
     float s = 0.f;
     for (int e = lane; e < E; e += 64) s = fmaf(src[e], src[e], s);
     const float nrm = fmaxf(sqrtf(wave_sum(s)), 1e-12f);
@@ -92,9 +94,9 @@ __device__ __forceinline__ void rt_stage(float* __restrict__ lds, int tid, const
 }
 
 // acc[m][n] = the wave's 32 x 32 score sub-tiles of the block (m0, n0): rows m0 + wm·64 + m·32 + .., columns n0 + wn·64 + n·32 + ..
-// Each element is fma(a_{E-1}, b_{E-1}, ... fma(a_0, b_0, 0)) in k order.  Ends with the block past its last LDS read.
-__device__ __forceinline__ void rt_tile_scores(const float* __restrict__ A, const float* __restrict__ B, int N, int E, size_t m0, size_t n0, float* As,
-                                               float* Bs, f32x16 (&acc)[2][2]) {
+// Each element is fma(a_{E-1}, b_{E-1}, ... fma(a_0, b_0, 0)) in k order.  A has NA rows, B has NB.  Ends with the block past its last LDS read.
+__device__ __forceinline__ void rt_tile_scores(const float* __restrict__ A, const float* __restrict__ B, int NA, int NB, int E, size_t m0, size_t n0,
+                                               float* As, float* Bs, f32x16 (&acc)[2][2]) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1;
 #pragma unroll
@@ -106,16 +108,16 @@ __device__ __forceinline__ void rt_tile_scores(const float* __restrict__ A, cons
     const float* ap = As + (wm * 64 + (lane & 31)) * RT_LD + (lane >> 5);
     const float* bp = Bs + (wn * 64 + (lane & 31)) * RT_LD + (lane >> 5);
     f32x4 va[4], vb[4];
-    rt_fetch(A, N, E, m0, 0, tid, va);
-    rt_fetch(B, N, E, n0, 0, tid, vb);
+    rt_fetch(A, NA, E, m0, 0, tid, va);
+    rt_fetch(B, NB, E, n0, 0, tid, vb);
     for (int k0 = 0; k0 < E; k0 += RT_BK) {
         __syncthreads();                                           // the previous step's fragment reads are done
         rt_stage(As, tid, va);
         rt_stage(Bs, tid, vb);
         __syncthreads();
         if (k0 + RT_BK < E) {
-            rt_fetch(A, N, E, m0, k0 + RT_BK, tid, va);
-            rt_fetch(B, N, E, n0, k0 + RT_BK, tid, vb);
+            rt_fetch(A, NA, E, m0, k0 + RT_BK, tid, va);
+            rt_fetch(B, NB, E, n0, k0 + RT_BK, tid, vb);
         }
 #pragma unroll
         for (int kk = 0; kk < RT_BK / 2; ++kk) {
@@ -140,7 +142,7 @@ __global__ __launch_bounds__(RT_THREADS) void rt_diag_kernel(int N, int E, const
     const int wm = wave >> 1, wn = wave & 1;
     const size_t t0 = (size_t)blockIdx.x * RT_TILE;
     f32x16 acc[2][2];
-    rt_tile_scores(A, B, N, E, t0, t0, As, Bs, acc);
+    rt_tile_scores(A, B, N, N, E, t0, t0, As, Bs, acc);
     if (wm != wn) return;                                          // the diagonal of the block lies in the waves (0, 0) and (1, 1), sub-tiles m == n
 #pragma unroll
     for (int m = 0; m < 2; ++m) {
@@ -179,7 +181,7 @@ __global__ __launch_bounds__(RT_THREADS, 2) void rt_rank_kernel(int N, int E, co
         cnt[3][u] = 0;
     }
     f32x16 acc[2][2];
-    rt_tile_scores(A, B, N, E, m0, n0, As, Bs, acc);           // its barriers order the writes above before the reads below
+    rt_tile_scores(A, B, N, N, E, m0, n0, As, Bs, acc);         // its barriers order the writes above before the reads below
     int cg[2] = {0, 0}, ce[2] = {0, 0};
     float dj[2];
     bool okj[2], badj[2];
@@ -398,6 +400,216 @@ __global__ __launch_bounds__(ST_THREADS) void st_final_kernel(int N, int nk, con
     }
 }
 
+// ------------------------------------------------------------------------------------------------ top-K listing
+// One total order on the candidates (score, gallery index) of a query: score descending by IEEE comparison (+0 == -0), equal scores by index ascending;
+// a NaN score is below every non-NaN score, NaN scores among themselves by index ascending.  An EMPTY list entry is (NaN, INT32_MAX): below every candidate.
+constexpr int TK_MAXK = 32;
+constexpr int TK_BLOCKS = 512;                     // the split rule aims at this many blocks: two per CU of a 256-CU device
+constexpr int TK_LDS = RT_TILE / 2 + 1;            // row stride of the staged half tile of scores, in floats
+constexpr int TK_EMPTY = 0x7fffffff;
+constexpr size_t TK_STAGE_BYTES = 2 * RT_TILE * RT_LD * sizeof(float);
+static_assert(RT_TILE * TK_LDS <= 2 * RT_TILE * RT_LD, "the staged half tile must fit into the operand stage");
+
+// The order as one unsigned comparison: tk_ord is monotonic in the score (both zeros one value, NaN the lowest), the low word falls with the index.
+// Only the comparisons use the key; the lists keep the score's own bits.
+constexpr size_t TK_EXTRA_BYTES = (1 + 4) * RT_TILE * sizeof(unsigned);       // per row: the worst entry's tk_ord, four 32-column pass masks
+
+__device__ __forceinline__ unsigned tk_ord(float s) {
+    unsigned u = __builtin_bit_cast(unsigned, s);
+    u = u == 0x80000000u ? 0u : u;                                 // -0 == +0
+    const unsigned o = u ^ ((unsigned)((int)u >> 31) | 0x80000000u);
+    return s != s ? 0u : o;                                        // below -inf, whose value is 0x007fffff
+}
+__device__ __forceinline__ unsigned long long tk_key(float s, int i) { return ((unsigned long long)tk_ord(s) << 32) | (unsigned)~i; }
+__device__ __forceinline__ bool tk_better(float s, int i, float t, int j) { return tk_key(s, i) > tk_key(t, j); }
+
+struct TopkLayout {
+    size_t an, bn, ps, pi, total;
+    int max_splits;
+};
+
+int topk_rule(int Q, int N) {
+    const int rt = (Q + RT_TILE - 1) / RT_TILE, ct = (N + RT_TILE - 1) / RT_TILE;
+    const int want = rt >= TK_BLOCKS ? 1 : TK_BLOCKS / rt;
+    return want < ct ? want : ct;
+}
+
+TopkLayout topk_layout(int Q, int N, int E, int K) {
+    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    TopkLayout l;
+    l.max_splits = topk_rule(Q, N);                // an explicit split count is held to the rule's: the partial lists never outgrow TK_BLOCKS·128·K entries
+    const size_t part = l.max_splits > 1 ? (size_t)l.max_splits * Q * K : 0;
+    l.an = 0;                                      // float [Q][E]: normalised queries (normalize != 0 only)
+    l.bn = up((size_t)Q * E * sizeof(float));      // float [N][E]: normalised gallery
+    l.ps = l.bn + up((size_t)N * E * sizeof(float));       // float [splits][Q][K]: partial lists, scores
+    l.pi = l.ps + up(part * sizeof(float));        // int   [splits][Q][K]: partial lists, gallery indices
+    l.total = l.pi + up(part * sizeof(int));
+    return l;
+}
+
+// Pass 1: block (x = row tile, y = split) owns 128 query rows and the gallery tiles [y·T/S, (y+1)·T/S) of the T column tiles.  Each tile's scores come from
+// rt_tile_scores.  Selection in three steps per tile:
+//   1. every lane tests its 64 accumulators against tk_ord of its rows' worst list entries (LDS, one word per row): score only, so a superset of what can
+//      enter, and padding columns masked by index.  A wave ballot per (register, sub-tile) gives each row a 32-column pass mask, four masks per row.
+//   2. the scores are staged half a tile at a time in the operand stage (free between two tiles);
+//   3. thread r < 128 owns row r: it walks the set bits of the row's masks, tests each flagged score exactly against the row's worst entry (kept in
+//      registers) and lets a winner take that entry's slot; K reads then find the new worst.  The list (LDS, [K][128]: entry j of every row side by side)
+//      is therefore UNORDERED while it grows.  Once the lists are warm a tile flags a handful of scores, and the serial part is a few steps.
+// The order is total, so the K entries after the last tile are the strip's first K whatever the tile order; they are written in order.
+// Dynamic LDS: the operand stage, K·128 entries, 5·128 words of thresholds and masks.
+static_assert(RT_TILE == 128, "the list epilogue splits its index with >> 7");
+__global__ __launch_bounds__(RT_THREADS, 2) void tk_list_kernel(int Q, int N, int E, int K, const float* __restrict__ A, const float* __restrict__ B,
+                                                             int* __restrict__ out_i, float* __restrict__ out_s) {
+    extern __shared__ __attribute__((aligned(16))) float tk_smem[];
+    float* As = tk_smem;
+    float* Bs = tk_smem + RT_TILE * RT_LD;
+    float* stage = tk_smem;                                        // aliases As / Bs: used only between two rt_tile_scores calls
+    float* ls = tk_smem + 2 * RT_TILE * RT_LD;
+    int* li = (int*)(ls + K * RT_TILE);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wm = wave >> 1, wn = wave & 1, half = lane >> 5, c = lane & 31;
+    const size_t m0 = (size_t)blockIdx.x * RT_TILE;
+    const int ct = (N + RT_TILE - 1) / RT_TILE;
+    const int t_begin = (int)((long long)blockIdx.y * ct / gridDim.y), t_end = (int)((long long)(blockIdx.y + 1) * ct / gridDim.y);
+    const float nan = __builtin_nanf("");
+    unsigned* tho = (unsigned*)(li + K * RT_TILE);                 // [128]: tk_ord of each row's worst entry (0 while the list has empty slots)
+    unsigned* msk = tho + RT_TILE;                                 // [4][128]: word wn·2 + n of a row flags its columns wn·64 + n·32 + 0 .. 31
+    for (int t = tid; t < K * RT_TILE; t += RT_THREADS) {
+        ls[t] = nan;
+        li[t] = TK_EMPTY;
+    }
+    if (tid < RT_TILE) tho[tid] = 0u;
+    unsigned long long thr = tk_key(nan, TK_EMPTY);                // the row's worst entry and its slot (threads below 128, which own row tid)
+    int thr_j = 0;
+    const bool row_ok = tid < RT_TILE && m0 + tid < (size_t)Q;
+    for (int tn = t_begin; tn < t_end; ++tn) {
+        const size_t n0 = (size_t)tn * RT_TILE;
+        f32x16 acc[2][2];
+        rt_tile_scores(A, B, Q, N, E, m0, n0, As, Bs, acc);       // its barriers order the initialisation above before the first scan
+        bool okj[2];
+#pragma unroll
+        for (int n = 0; n < 2; ++n) okj[n] = n0 + (size_t)(wn * 64 + n * 32 + c) < (size_t)N;            // by index: padding is never selectable
+#pragma unroll
+        for (int m = 0; m < 2; ++m)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int lr = wm * 64 + m * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+                const unsigned t = tho[lr];
+#pragma unroll
+                for (int n = 0; n < 2; ++n) {
+                    const unsigned long long b = __ballot(okj[n] && tk_ord(acc[m][n][r]) >= t);
+                    if (c == 0) msk[(wn * 2 + n) * RT_TILE + lr] = half ? (unsigned)(b >> 32) : (unsigned)b;
+                }
+            }
+        for (int h = 0; h < 2; ++h) {
+            if (wn == h) {
+#pragma unroll
+                for (int m = 0; m < 2; ++m)
+#pragma unroll
+                    for (int n = 0; n < 2; ++n)
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) {
+                            const int lr = wm * 64 + m * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
+                            stage[lr * TK_LDS + n * 32 + c] = acc[m][n][r];
+                        }
+            }
+            __syncthreads();
+            if (row_ok) {
+                const int g0 = (int)n0 + h * (RT_TILE / 2);
+                const float* row = stage + tid * TK_LDS;
+                bool changed = false;
+#pragma unroll
+                for (int n = 0; n < 2; ++n) {
+                    unsigned mk = msk[(h * 2 + n) * RT_TILE + tid];
+                    while (mk) {
+                        const int cc = n * 32 + __builtin_ctz(mk);
+                        mk &= mk - 1;
+                        const float v = row[cc];
+                        const int g = g0 + cc;
+                        if (tk_key(v, g) <= thr) continue;
+                        ls[thr_j * RT_TILE + tid] = v;                          // takes the worst entry's slot; then the new worst of the K
+                        li[thr_j * RT_TILE + tid] = g;
+                        changed = true;
+                        thr = tk_key(ls[tid], li[tid]);
+                        thr_j = 0;
+#pragma unroll 4
+                        for (int j = 1; j < K; ++j) {
+                            const unsigned long long e = tk_key(ls[j * RT_TILE + tid], li[j * RT_TILE + tid]);
+                            if (e < thr) {                                      // equal (empty) entries: the first stays the worst
+                                thr = e;
+                                thr_j = j;
+                            }
+                        }
+                    }
+                }
+                if (changed) tho[tid] = (unsigned)(thr >> 32);
+            }
+            __syncthreads();                                       // the stage is free again: for the other half, then for the next tile's operands
+        }
+    }
+    __syncthreads();                                               // a strip without tiles never met a barrier
+    // The lists leave in order: entry j of row r goes to the place that the number of the row's entries before it gives (empty entries, all equal, keep
+    // their slot order behind the candidates).  Row r is lane-contiguous in LDS, so every read below is conflict-free.
+    const int rows = (size_t)Q - m0 < RT_TILE ? (int)((size_t)Q - m0) : RT_TILE;
+    const size_t base = ((size_t)blockIdx.y * Q + m0) * K;        // [split][Q][K]; the one list [Q][K] when there is one split
+    for (int t = tid; t < K * RT_TILE; t += RT_THREADS) {
+        const int r = t & (RT_TILE - 1), j = t >> 7;
+        if (r >= rows) continue;
+        const float s = ls[t];
+        const int i = li[t];
+        int place = 0;
+        for (int o = 0; o < K; ++o) {
+            const float os = ls[o * RT_TILE + r];
+            const int oi = li[o * RT_TILE + r];
+            place += (tk_better(os, oi, s, i) || (oi == i && o < j)) ? 1 : 0;
+        }
+        out_s[base + (size_t)r * K + place] = s;
+        out_i[base + (size_t)r * K + place] = i;
+    }
+}
+
+// Pass 2: one wave per query row.  Place r of the result is the best of the row's S·K partial entries that comes strictly after place r - 1 in the order;
+// candidates carry distinct gallery indices, so K rounds of a wave-wide minimum give the first K of the union.  (Empty entries are never reached: the
+// strips together hold min(N, S·K) >= K candidates.)
+__global__ __launch_bounds__(256) void tk_merge_kernel(int Q, int K, int S, const float* __restrict__ ps, const int* __restrict__ pi, int* __restrict__ idx,
+                                                       float* __restrict__ score) {
+    const size_t q = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63;
+    if (q >= (size_t)Q) return;
+    const int M = S * K;
+    float prev_s = 0.f;
+    int prev_i = -1;
+    for (int r = 0; r < K; ++r) {
+        float best_s = __builtin_nanf("");
+        int best_i = TK_EMPTY;
+        for (int e = lane; e < M; e += 64) {
+            const int s = e / K, j = e - s * K;
+            const size_t at = ((size_t)s * Q + q) * K + j;
+            const float vs = ps[at];
+            const int vi = pi[at];
+            if ((r == 0 || tk_better(prev_s, prev_i, vs, vi)) && tk_better(vs, vi, best_s, best_i)) {
+                best_s = vs;
+                best_i = vi;
+            }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const float os = __shfl_xor(best_s, o, 64);
+            const int oi = __shfl_xor(best_i, o, 64);
+            if (tk_better(os, oi, best_s, best_i)) {
+                best_s = os;
+                best_i = oi;
+            }
+        }
+        if (lane == 0) {
+            idx[q * K + r] = best_i;
+            score[q * K + r] = best_s;
+        }
+        prev_s = best_s;
+        prev_i = best_i;
+    }
+}
+
 }  // namespace
 
 size_t uia_retrieval_ranks_ws_bytes(int N, int E) {
@@ -426,7 +638,7 @@ int uia_retrieval_ranks_launch(hipStream_t stream, int N, int E, const float* im
     if (normalize) {
         float* an = (float*)(base + l.an);
         float* bn = (float*)(base + l.bn);
-        hipLaunchKernelGGL(rt_normalize_kernel, dim3((unsigned)((2 * (size_t)N + 3) / 4)), dim3(256), 0, stream, N, E, img, txt, an, bn);
+        hipLaunchKernelGGL(rt_normalize_kernel, dim3((unsigned)((2 * (size_t)N + 3) / 4)), dim3(256), 0, stream, N, N, E, img, txt, an, bn);
         A = an;
         B = bn;
     }
@@ -461,6 +673,53 @@ int uia_retrieval_stats_launch(hipStream_t stream, int N, const int32_t* gt, int
     hipLaunchKernelGGL(st_pick_hi_kernel, dim3(1), dim3(ST_THREADS), 0, stream, N, head, hist_hi);
     hipLaunchKernelGGL(st_lo_kernel, dim3(blocks), dim3(ST_THREADS), 0, stream, N, gt, head, hist_lo);
     hipLaunchKernelGGL(st_final_kernel, dim3(1), dim3(ST_THREADS), 0, stream, N, nk, head, hist_lo, record);
+    UIA_CHECK_LAUNCH();
+    return 0;
+}
+
+size_t uia_retrieval_topk_ws_bytes(int Q, int N, int E, int K) {
+    if (Q < 1 || Q > RT_MAXN || N < 1 || N > RT_MAXN || E < 4 || E > RT_MAXE || E % 4 != 0 || K < 1 || K > TK_MAXK || K > N) return 0;
+    return topk_layout(Q, N, E, K).total;
+}
+
+int uia_retrieval_topk_rule(int Q, int N) {
+    if (Q < 1 || Q > RT_MAXN || N < 1 || N > RT_MAXN) return 1;
+    return topk_rule(Q, N);
+}
+
+int uia_retrieval_topk_launch(hipStream_t stream, int Q, int N, int E, int K, const float* queries, const float* gallery, int normalize, int splits, void* ws,
+                              size_t ws_bytes, int32_t* idx, float* score) {
+    UIA_CHECK_ARG(Q >= 1 && Q <= RT_MAXN && N >= 1 && N <= RT_MAXN && E >= 4 && E <= RT_MAXE && E % 4 == 0,
+                  "uia_retrieval_topk: bad shape Q=%d N=%d E=%d (1 <= Q, N <= %d, 4 <= E <= %d, E %% 4 == 0)", Q, N, E, RT_MAXN, RT_MAXE);
+    UIA_CHECK_ARG(K >= 1 && K <= TK_MAXK && K <= N, "uia_retrieval_topk: bad K=%d (1 <= K <= min(N, %d), N=%d)", K, TK_MAXK, N);
+    UIA_CHECK_ARG(queries && gallery && ws && idx && score, "uia_retrieval_topk: null tensor");
+    UIA_CHECK_ARG(((uintptr_t)queries | (uintptr_t)gallery | (uintptr_t)ws) % 16 == 0,
+                  "uia_retrieval_topk: queries, gallery and the workspace must be 16-byte aligned");
+    UIA_CHECK_ARG(((uintptr_t)idx | (uintptr_t)score) % 4 == 0, "uia_retrieval_topk: idx and score must be 4-byte aligned");
+    const TopkLayout l = topk_layout(Q, N, E, K);
+    UIA_CHECK_ARG(splits >= 0 && splits <= TK_BLOCKS, "uia_retrieval_topk: bad splits=%d (0 = the rule, else 1 .. %d)", splits, TK_BLOCKS);
+    UIA_CHECK_ARG(ws_bytes >= l.total, "uia_retrieval_topk: workspace of %zu bytes, %zu needed", ws_bytes, l.total);
+    const int S = splits == 0 || splits > l.max_splits ? l.max_splits : splits;        // never more strips than the rule's: that is what the workspace holds
+    const size_t lds = TK_STAGE_BYTES + (size_t)K * RT_TILE * (sizeof(float) + sizeof(int)) + TK_EXTRA_BYTES;
+    static UiaDevOnce once;                                        // K = 32 takes 69 120 B, past the 64 KiB a kernel gets unasked
+    UIA_ENSURE_LDS_ATTR(once, tk_list_kernel, (int)(TK_STAGE_BYTES + (size_t)TK_MAXK * RT_TILE * (sizeof(float) + sizeof(int)) + TK_EXTRA_BYTES));
+    char* base = (char*)ws;
+    const float* A = queries;
+    const float* B = gallery;
+    if (normalize) {
+        float* an = (float*)(base + l.an);
+        float* bn = (float*)(base + l.bn);
+        hipLaunchKernelGGL(rt_normalize_kernel, dim3((unsigned)(((size_t)Q + (size_t)N + 3) / 4)), dim3(256), 0, stream, Q, N, E, queries, gallery, an, bn);
+        A = an;
+        B = bn;
+    }
+    const int row_tiles = (Q + RT_TILE - 1) / RT_TILE;
+    float* part_s = (float*)(base + l.ps);
+    int* part_i = (int*)(base + l.pi);
+    hipLaunchKernelGGL(tk_list_kernel, dim3((unsigned)row_tiles, (unsigned)S), dim3(RT_THREADS), lds, stream, Q, N, E, K, A, B, S == 1 ? idx : part_i,
+                       S == 1 ? score : part_s);
+    if (S > 1)
+        hipLaunchKernelGGL(tk_merge_kernel, dim3((unsigned)(((size_t)Q + 3) / 4)), dim3(256), 0, stream, Q, K, S, part_s, part_i, idx, score);
     UIA_CHECK_LAUNCH();
     return 0;
 }

@@ -96,6 +96,10 @@ int uia_retrieval_ranks_launch(hipStream_t stream, int N, int E, const float* im
                                int32_t* gt_i2t, int32_t* eq_i2t, int32_t* gt_t2i, int32_t* eq_t2i);
 size_t uia_retrieval_stats_ws_bytes(int N);
 int uia_retrieval_stats_launch(hipStream_t stream, int N, const int32_t* gt, int nk, const int32_t* k_values, void* ws, size_t ws_bytes, double* record);
+size_t uia_retrieval_topk_ws_bytes(int Q, int N, int E, int K);
+int uia_retrieval_topk_rule(int Q, int N);
+int uia_retrieval_topk_launch(hipStream_t stream, int Q, int N, int E, int K, const float* queries, const float* gallery, int normalize, int splits, void* ws,
+                              size_t ws_bytes, int32_t* idx, float* score);
 size_t uia_augment_ws_bytes(int B, int S);
 int uia_augment_batch_launch(hipStream_t stream, int B, int S, const float* images, const uint8_t* masks, const int32_t* programs, void* ws, size_t ws_bytes,
                              float* out_images, uint8_t* out_masks);

@@ -8,6 +8,11 @@ whole split (:179-213), the metric keys, the result block, results.csv (`Metric,
 
 Different: the features stay on the device (the reference moves every batch to the CPU, :205-206) and the metrics are two HIP calls that never form
 the n x n score matrix (uia_retrieval_ranks / uia_retrieval_stats), one host copy for the lot.  Data: `--synthetic` or `--data_pt {"images", "captions"}`.
+
+Added, off by default: `--topk K` lists each query's K best candidates in both directions (topk_i2t.csv, topk_t2i.csv beside results.csv, and "topk" in
+features.pth) from the fused top-K kernel (uia_retrieval_topk: the same score tiles, equal scores by candidate index), and logs hit@K, the share of queries
+whose own pair is in their list (at most R@K, whose tie rule is optimistic); `--queries_txt FILE` retrieves the K best images of the split for each line of
+free text (topk_queries.csv).  Neither changes the metrics or results.csv.
 """
 import argparse
 import logging
@@ -23,9 +28,11 @@ from src.adapters import inject_lora_to_biomedclip, inject_mona_variant_to_open_
 from src.datasets.rocov2 import ROCOv2DataModule
 from src.models.biomedclip.zero_shot import load_adapter_by_name
 from src.third_party.biomedclip.model import SyntheticTokenizer, create_biomedclip
-from src.utils.retrieval_metrics import compute_retrieval_metrics, log_retrieval_metrics
+from src.utils.retrieval_metrics import compute_retrieval_metrics, hit_at_k, log_retrieval_metrics, retrieve_topk, write_topk_csv
 from src.utils.tools import default_device, parse_config, setup_logging
 from uia_hip import functional as UF
+
+TOPK_MAX = 32                                           # the limit of uia_retrieval_topk
 
 
 def get_args(argv=None):
@@ -66,7 +73,14 @@ def get_args(argv=None):
     parser.add_argument("--data_pt", type=str, default=None, help=".pt with {'images': [N,1|3,S,S], 'captions': [N] str}")
     parser.add_argument("--ckpt_path", type=str, default=None, help="pretrained BiomedCLIP state dict (the reference downloads it by --model_name)")
     parser.add_argument("--model_config", type=str, default=None)
-    return parser.parse_args(argv)
+    parser.add_argument("--topk", type=int, default=0, help="list each query's K best candidates (topk_i2t.csv, topk_t2i.csv); 0 = off, at most 32")
+    parser.add_argument("--queries_txt", type=str, default=None, help="one free-text query per line: the K best images of the split for each (topk_queries.csv); needs --topk")
+    args = parser.parse_args(argv)
+    if not 0 <= args.topk <= TOPK_MAX:
+        parser.error(f"--topk {args.topk}: the listing holds at most {TOPK_MAX} candidates per query")
+    if args.queries_txt is not None and args.topk == 0:
+        parser.error("--queries_txt needs --topk K")
+    return args
 
 
 def load_model(args):
@@ -126,8 +140,33 @@ def result_rows(k_values, metrics):
     return rows
 
 
-def save_results(args, metrics, image_features=None, text_features=None, captions=None):
-    """reference :216-297: <output_dir>/<time>_rsum=<rsum>/ with results.csv, the log and, with --save_features, features.pth; returns the folder."""
+@torch.no_grad()
+def topk_listings(model, tokenizer, image_features, text_features, args):
+    """--topk: {"i2t": (idx, score), "t2i": (idx, score)} and, with --queries_txt, "queries" (the file's lines against the images) with the lines
+    themselves; CPU tensors [n, K], K = min(--topk, n).  One line per paired direction with hit@K for each --k_values entry <= K."""
+    n = image_features.shape[0]
+    K = min(args.topk, n)
+    listings = {}
+    for d, title, q, g in (("i2t", "Image-to-Text", image_features, text_features), ("t2i", "Text-to-Image", text_features, image_features)):
+        idx, score = retrieve_topk(q, g, K, normalize=True)
+        hits = hit_at_k(idx, args.k_values)
+        logging.info(f"[{args.split}] {title} top-{K} listing: " + "  ".join(f"hit@{k}: {v:.2f}" for k, v in hits.items()))
+        listings[d] = (idx.cpu(), score.cpu())
+    lines = None
+    if args.queries_txt is not None:
+        with open(args.queries_txt) as f:
+            lines = [ln.strip() for ln in f if ln.strip()]
+        if not lines:
+            raise RuntimeError(f"--queries_txt {args.queries_txt}: no query lines")
+        feats = [model.encode_text(tokenizer(lines[i:i + args.batch_size]).to(args.device)).float() for i in range(0, len(lines), args.batch_size)]
+        idx, score = retrieve_topk(torch.cat(feats, dim=0), image_features, K, normalize=True)
+        listings["queries"] = (idx.cpu(), score.cpu())
+    return listings, lines
+
+
+def save_results(args, metrics, image_features=None, text_features=None, captions=None, listings=None, query_lines=None):
+    """reference :216-297: <output_dir>/<time>_rsum=<rsum>/ with results.csv, the log and, with --save_features, features.pth; with --topk the listings
+    topk_i2t.csv / topk_t2i.csv (/ topk_queries.csv); returns the folder."""
     import datetime
     import shutil
     backup_folder = os.path.join(args.output_dir, f"{datetime.datetime.now().strftime('%Y_%m_%d_%H_%M_%S')}_rsum={metrics['rsum']:.2f}")
@@ -150,9 +189,17 @@ def save_results(args, metrics, image_features=None, text_features=None, caption
     result_str += f"rSum: {metrics['rsum']:.2f}\n"
     result_str += f"{'=' * 50}\n"
     logging.info(result_str)
+    if listings:
+        for d, (idx, score) in listings.items():
+            listing_path = os.path.join(backup_folder, f"topk_{d}.csv")
+            write_topk_csv(listing_path, idx, score, query_lines if d == "queries" else captions, d)
+            logging.info(f"Top-{idx.shape[1]} listing saved to: {listing_path}")
     if args.save_features and image_features is not None and text_features is not None:
         features_file = os.path.join(backup_folder, "features.pth")
-        torch.save({"image_features": image_features.cpu(), "text_features": text_features.cpu(), "captions": captions, "metrics": metrics}, features_file)
+        saved = {"image_features": image_features.cpu(), "text_features": text_features.cpu(), "captions": captions, "metrics": metrics}
+        if listings:
+            saved["topk"] = {d: listings[d] for d in ("i2t", "t2i")}
+        torch.save(saved, features_file)
         logging.info(f"Features saved to: {features_file}")
     for h in list(logging.getLogger().handlers):
         h.flush()
@@ -181,7 +228,8 @@ def main(argv=None):
     image_features, text_features, captions = extract_features(model, tokenizer, dataloader, args)
     metrics = compute_retrieval_metrics(image_features, text_features, k_values=args.k_values, normalize=True)
     log_retrieval_metrics(metrics, prefix=args.split)
-    args.backup_folder = save_results(args, metrics, image_features, text_features, captions)
+    listings, query_lines = topk_listings(model, tokenizer, image_features, text_features, args) if args.topk > 0 else (None, None)
+    args.backup_folder = save_results(args, metrics, image_features, text_features, captions, listings, query_lines)
     logging.info("✓ Retrieval evaluation complete")
     return metrics
 

@@ -8,7 +8,12 @@ but never shipped.  The call signatures and the keys the entry point reads (:233
     and t2i; `rsum` is the sum of every R@K of both directions.
 
 Everything up to the record runs on the device: `uia_retrieval_ranks` forms score tiles on the fp32 matrix cores and reduces them to rank counts without
-writing the n x n matrix, `uia_retrieval_stats` turns one direction's counts into R@K / median / mean.  One host copy brings both records and the tie counts."""
+writing the n x n matrix, `uia_retrieval_stats` turns one direction's counts into R@K / median / mean.  One host copy brings both records and the tie counts.
+
+The listing behind the table is `retrieve_topk` (`uia_retrieval_topk`: the same score tiles with a selection epilogue): each query's K best candidates,
+score descending, EQUAL scores by candidate index ascending, NaN scores last.  That tie rule is by index where the metrics' is optimistic, so the share of
+queries whose own pair is in their K-list (`hit_at_k`) is at most R@K; the gap is what ties are worth.  `write_topk_csv` writes a listing as a table."""
+import csv
 import logging
 
 import torch
@@ -52,3 +57,35 @@ def log_retrieval_metrics(metrics, prefix=""):
     if "n" in metrics:
         extra = f"  (n={int(metrics['n'])}, queries with ties: i2t {int(metrics.get('i2t_ties', 0))}, t2i {int(metrics.get('t2i_ties', 0))})"
     logging.info(f"{tag}rSum: {metrics['rsum']:.2f}{extra}")
+
+
+def retrieve_topk(query_features, gallery_features, k, normalize=True):
+    """query_features [Q, D], gallery_features [N, D] device tensors, 1 <= k <= min(N, 32) -> (idx int32 [Q, k], score fp32 [Q, k]) device tensors:
+    idx[q, r] is the gallery row at place r + 1 for query q (order above), score[q, r] its score.  The Q x N matrix is never formed."""
+    from uia_hip import ops
+    return ops.retrieval_topk(query_features, gallery_features, int(k), normalize=normalize)
+
+
+def hit_at_k(idx, k_values):
+    """idx [n, K] of a PAIRED listing (query i belongs to candidate i) -> {k: percent of queries whose own pair is among their first k} for each k <= K."""
+    n, K = idx.shape
+    own = idx == torch.arange(n, device=idx.device, dtype=idx.dtype)[:, None]
+    return {int(k): 100.0 * float(own[:, :int(k)].any(1).sum()) / n for k in k_values if int(k) <= K}
+
+
+TOPK_COLUMNS = ("query_index", "rank", "candidate_index", "score", "is_pair", "caption")
+
+
+def write_topk_csv(path, idx, score, captions, direction):
+    """One row per (query, place): query_index, rank (1-based), candidate_index, score (%.6f), is_pair (candidate_index == query_index) and the text side of
+    the row: the candidate's caption for direction "i2t", the query's caption for "t2i".  Direction "queries" is free-text queries against the images:
+    `captions` are the query lines, caption is the query's and is_pair is always 0."""
+    assert direction in ("i2t", "t2i", "queries"), direction
+    idx, score = torch.as_tensor(idx).cpu().tolist(), torch.as_tensor(score).cpu().tolist()
+    with open(path, "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(TOPK_COLUMNS)
+        for q, (row_i, row_s) in enumerate(zip(idx, score)):
+            for r, (c, s) in enumerate(zip(row_i, row_s)):
+                pair = int(c == q) if direction != "queries" else 0
+                w.writerow([q, r + 1, c, f"{s:.6f}", pair, captions[c] if direction == "i2t" else captions[q]])

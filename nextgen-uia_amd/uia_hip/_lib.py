@@ -159,6 +159,9 @@ PROTOTYPES = {
     "uia_retrieval_ranks": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, C.c_int, vp, sz, vp, vp, vp, vp]),
     "uia_retrieval_stats_workspace_bytes": (sz, [C.c_int]),
     "uia_retrieval_stats": (C.c_int, [vp, C.c_int, vp, C.c_int, vp, vp, sz, vp]),
+    "uia_retrieval_topk_workspace_bytes": (sz, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "uia_retrieval_topk_splits": (C.c_int, [C.c_int, C.c_int]),
+    "uia_retrieval_topk": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp, sz, vp, vp]),
     "uia_augment_workspace_bytes": (sz, [C.c_int, C.c_int]),
     "uia_augment_batch": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp, vp, sz, vp, vp]),
     "uia_infonce_workspace_bytes": (sz, [C.c_int, C.c_int]),

@@ -1766,6 +1766,24 @@ def retrieval_ranks(img, txt, normalize=True):
     return out[0], out[1], out[2], out[3]
 
 
+def retrieval_topk(queries, gallery, k, normalize=True, splits=0):
+    """queries [Q, E], gallery [N, E] (non-fp32 is converted), 1 <= k <= min(N, 32) -> (idx int32 [Q, k], score fp32 [Q, k]) device tensors: for each query
+    its k best gallery rows, score descending, equal scores by gallery index ascending, NaN scores last; the same score bits as retrieval_ranks.  The
+    Q x N score matrix is never formed.  splits: gallery strips per row tile, 0 = the kernel's rule (the result does not depend on it).  Enqueued only."""
+    _p(queries), _p(gallery)                                      # CPU tensors are refused before anything else
+    assert queries.dim() == 2 and gallery.dim() == 2 and queries.shape[1] == gallery.shape[1] and queries.device == gallery.device, \
+        f"retrieval_topk: queries {tuple(queries.shape)} and gallery {tuple(gallery.shape)} must be [Q, E] and [N, E] on one device"
+    a, b = queries.detach().float().contiguous(), gallery.detach().float().contiguous()
+    (Q, E), N, K = a.shape, b.shape[0], int(k)
+    need = lib().uia_retrieval_topk_workspace_bytes(Q, N, E, K)
+    ws = torch.empty(max(need, 16), device=a.device, dtype=torch.uint8)        # need == 0: a shape outside the limits, which the call below names
+    idx = torch.empty(Q, max(K, 0), device=a.device, dtype=torch.int32)
+    score = torch.empty(Q, max(K, 0), device=a.device, dtype=torch.float32)
+    check(lib().uia_retrieval_topk(_stream(), Q, N, E, K, _p(a), _p(b), 1 if normalize else 0, int(splits), _p(ws), need, _p(idx), _p(score)),
+          "uia_retrieval_topk")
+    return idx, score
+
+
 def retrieval_stats(gt, k_values):
     """gt int32 [N] (one direction of retrieval_ranks), k_values a sequence of K -> fp64 device record [len(k_values) + 2]: R@K in percent for each K, the
     median and the mean of rank = 1 + gt."""
