@@ -505,6 +505,28 @@ size_t uia_retrieval_topk_workspace_bytes(int Q, int N, int E, int K);
 int uia_retrieval_topk_splits(int Q, int N);
 int uia_retrieval_topk(void* stream, int Q, int N, int E, int K, const float* queries, const float* gallery, int normalize, int splits, void* ws,
                        size_t ws_bytes, int32_t* idx, float* score);
+/* Zero-shot classification scores of one batch of image features (the rule of the reference's src/models/metaclip/zero_shot.py:162-182 and
+ * biomedclip/zero_shot.py:176-222), one launch.  img fp32 [N,E] and prompts fp32 [T,E], raw tower outputs, row-major contiguous; class_off a HOST
+ * array int32 [C+1]: class c owns the prompt rows class_off[c] .. class_off[c+1]-1 (class_off[0] == 0, class_off[C] == T; ragged classes allowed).
+ * Limits, checked before anything is enqueued (non-zero, uia_last_error(), nothing launched): 2 <= C <= 8, 1 <= prompts per class <= 32, T <= 256,
+ * 1 <= E <= 4096, 1 <= N <= 2^24, ld >= C, row >= 0.  Every row is divided by its L2 norm with NO eps (x / x.norm()): a zero image row gives NaN logits
+ * for that image, a zero prompt row NaN for its class in every image; NaN is never an index.  s[i,t] = 100 * <img_n[i], prm_n[t]> on the exact fp32
+ * MFMA (a k-ordered fmaf chain from 0); logits[i,c] = the fp32 sum of s[i,t] over the class's prompts in prompt order, divided once by their count.
+ * The bits of logits[i,:] depend only on row i of img and on prompts, never on N or on the row's place in the batch: any batching gives the same table.
+ * Outputs: logits fp32, row i at logits + (row + i) * ld (a whole split lands in one buffer; only those N rows, C values each, are written);
+ * probs fp32 [N,C] contiguous or NULL: softmax of the logits, log-sum-exp form evaluated in fp64 (finite for logits of +-100); img_n fp32 [N,E]
+ * contiguous or NULL: the normalised image rows.  Asynchronous, deterministic (no atomics), no workspace. */
+int uia_zero_shot_score(void* stream, int N, int T, int E, int C, const int32_t* class_off, const float* img, const float* prompts, float* logits, int64_t ld,
+                        int64_t row, float* probs, float* img_n);
+/* The exact ROC curve of a split, as torchmetrics ROC(task="binary", thresholds=None) returns it.  p1 fp32 [N], labels int64 [N] in {0,1}, perm int64 [N]:
+ * the permutation that sorts p1 ascending (as for uia_binary_cls_stats); 1 <= N <= 2^24.  Outputs on the device: count int32 [1], fpr and tpr fp64 [N+1],
+ * thr fp32 [N+1].  Point 0 is (0, 0, thr = 1.0); then one point per distinct score in descending order, fpr = #{neg : p1 >= thr} / #neg,
+ * tpr = #{pos : p1 >= thr} / #pos (integer counts, one fp64 division each; the axis of an absent class is all zeros); count = distinct scores + 1, and
+ * entries from count on are left as they were.  A label outside {0,1}, a perm entry outside [0,N) or a NaN score gives count = -1 and leaves the arrays
+ * unwritten.  One workgroup, group ends compacted with a scan: deterministic, no atomics.  ws: uia_binary_roc_curve_workspace_bytes(N) of scratch. */
+size_t uia_binary_roc_curve_workspace_bytes(int N);
+int uia_binary_roc_curve(void* stream, int N, const float* p1, const int64_t* labels, const int64_t* perm, void* ws, size_t ws_bytes, int32_t* count,
+                         double* fpr, double* tpr, float* thr);
 
 /* Training-time augmentation of a batch, one launch (the reference's src/datasets/{segmentation,classification}.py:14-156 on the device).  images fp32
  * [B,1,S,S] in [0,1] (4-byte aligned; 16-byte accesses where an image starts on 16 bytes), masks uint8 [B,1,S,S] or NULL (then out_masks is NULL too),

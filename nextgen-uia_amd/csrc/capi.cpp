@@ -257,6 +257,16 @@ int uia_retrieval_topk(void* stream, int Q, int N, int E, int K, const float* qu
     return uia_retrieval_topk_launch((hipStream_t)stream, Q, N, E, K, queries, gallery, normalize, splits, ws, ws_bytes, idx, score);
 }
 
+int uia_zero_shot_score(void* stream, int N, int T, int E, int C, const int32_t* class_off, const float* img, const float* prompts, float* logits, int64_t ld,
+                        int64_t row, float* probs, float* img_n) {
+    return uia_zero_shot_score_launch((hipStream_t)stream, N, T, E, C, class_off, img, prompts, logits, (long)ld, (long)row, probs, img_n);
+}
+size_t uia_binary_roc_curve_workspace_bytes(int N) { return uia_binary_roc_curve_ws_bytes(N); }
+int uia_binary_roc_curve(void* stream, int N, const float* p1, const int64_t* labels, const int64_t* perm, void* ws, size_t ws_bytes, int32_t* count,
+                         double* fpr, double* tpr, float* thr) {
+    return uia_binary_roc_curve_launch((hipStream_t)stream, N, p1, labels, perm, ws, ws_bytes, count, fpr, tpr, thr);
+}
+
 size_t uia_augment_workspace_bytes(int B, int S) { return uia_augment_ws_bytes(B, S); }
 int uia_augment_batch(void* stream, int B, int S, const float* images, const uint8_t* masks, const int32_t* programs, void* ws, size_t ws_bytes,
                       float* out_images, uint8_t* out_masks) {

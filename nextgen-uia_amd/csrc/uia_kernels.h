@@ -100,6 +100,11 @@ size_t uia_retrieval_topk_ws_bytes(int Q, int N, int E, int K);
 int uia_retrieval_topk_rule(int Q, int N);
 int uia_retrieval_topk_launch(hipStream_t stream, int Q, int N, int E, int K, const float* queries, const float* gallery, int normalize, int splits, void* ws,
                               size_t ws_bytes, int32_t* idx, float* score);
+int uia_zero_shot_score_launch(hipStream_t stream, int N, int T, int E, int C, const int32_t* class_off, const float* img, const float* prompts, float* logits,
+                               long ld, long row, float* probs, float* img_n);
+size_t uia_binary_roc_curve_ws_bytes(int N);
+int uia_binary_roc_curve_launch(hipStream_t stream, int N, const float* p1, const int64_t* labels, const int64_t* perm, void* ws, size_t ws_bytes,
+                                int32_t* count, double* fpr, double* tpr, float* thr);
 size_t uia_augment_ws_bytes(int B, int S);
 int uia_augment_batch_launch(hipStream_t stream, int B, int S, const float* images, const uint8_t* masks, const int32_t* programs, void* ws, size_t ws_bytes,
                              float* out_images, uint8_t* out_masks);

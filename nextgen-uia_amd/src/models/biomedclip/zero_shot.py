@@ -3,16 +3,15 @@
 
 Kept from the reference: the command line (:31-72), adapter loading by parameter NAME from a fine-tune checkpoint
 (`mona_state_dict` / `lora_state_dict` wrapper or a bare dict, :107-147 — names are the checkpoint wire format), eval mode,
-and the scoring rule (:176-222): class prototypes = L2-normalised text features of a prompt ensemble per class, logits[b, c] =
-mean over the class's prompts of 100 · <image feature, prompt feature>.  Host-side reporting (ROC figure, CSV, MONAI/
-torchmetrics accumulators, :224-290) is outside the hot path; this module returns accuracy, AUC and cross-entropy computed
-with a few torch ops.  The prompt ensembles are the reference's (src/models/zero_shot_prompt.py:29-54, carried as data: ten prompts per class, picked by
---dataset as in reference :168-173); --prompts_json overrides them.  Data: --synthetic or --data_pt {"images","labels"}.
+the scoring rule (:176-222): logits[b, c] = mean over the class's prompts of 100 · <normalised image feature, normalised prompt
+feature>, and the report (:224-290): Acc / Rec / Pre / F1 / AUC, the ROC curve and results.csv in a <time>_acc=<acc> folder.
+The loop, the scoring kernel and the report are src/models/zero_shot_eval.py's, shared with the MetaCLIP, CLIP and UniMed-CLIP
+entries; this module keeps the flags and the model.  The prompt ensembles are the reference's (src/models/zero_shot_prompt.py:29-54,
+carried as data: ten prompts per class, picked by --dataset as in reference :168-173); --prompts_json overrides them.
+Data: --synthetic or --data_pt {"images","labels"}.
 """
 import argparse
-import json
 import logging
-import os
 import sys
 from pathlib import Path
 
@@ -21,9 +20,10 @@ sys.path.insert(0, str(Path(__file__).resolve().parents[3]))
 import torch
 
 from src.adapters import inject_lora_to_biomedclip, inject_mona_variant_to_open_clip
-from src.models.zero_shot_prompt import ensemble_for
+from src.models import zero_shot_eval as ZS
+from src.models.zero_shot_prompt import ensemble_for  # noqa: F401  (the ensembles are part of this module's surface)
 from src.third_party.biomedclip.model import SyntheticTokenizer, create_biomedclip
-from src.utils.tools import parse_config, setup_logging
+from src.utils.tools import parse_config
 from uia_hip import functional as UF
 
 LESION_TYPES = ("benign", "malignant")
@@ -99,77 +99,20 @@ def prepare_model(args):
 
 
 def _test_batches(args):
-    if args.data_pt:
-        blob = torch.load(args.data_pt)
-        images, labels = blob["images"], blob["labels"].long()
-        images = images.float() / 255.0 if images.dtype == torch.uint8 else images.float()
-    elif args.synthetic:
-        g = torch.Generator().manual_seed(args.seed)
-        images = torch.rand(args.synthetic_test, 1, args.img_size, args.img_size, generator=g).repeat(1, 3, 1, 1)
-        labels = torch.randint(0, 2, (args.synthetic_test,), generator=g)
-    else:
-        raise RuntimeError("no dataset: pass --synthetic or --data_pt")
+    images, labels = ZS.load_test_split(args)
     for i in range(0, len(labels), args.batch_size):
         yield images[i:i + args.batch_size], labels[i:i + args.batch_size]
 
 
-def binary_auc(score, label):
-    """Area under the ROC curve by the rank statistic (ties get the average rank)."""
-    pos, neg = score[label == 1], score[label == 0]
-    if len(pos) == 0 or len(neg) == 0:
-        return float("nan")
-    cmp = (pos[:, None] > neg[None, :]).double() + 0.5 * (pos[:, None] == neg[None, :]).double()
-    return float(cmp.mean())
-
-
-@torch.no_grad()
-def class_text_features(model, tokenizer, prompts, device):
-    feats = {}
-    for c in LESION_TYPES:
-        f = model.encode_text(tokenizer(prompts[c]).to(device))
-        feats[c] = f / f.norm(dim=-1, keepdim=True)
-    return feats
-
-
-@torch.no_grad()
-def ensemble_logits(model, images, text_feats):
-    f = model.encode_image(images)
-    f = f / f.norm(dim=-1, keepdim=True)
-    return torch.stack([(100.0 * f @ text_feats[c].T).mean(dim=1) for c in LESION_TYPES], dim=1)      # [B, 2]
-
-
 @torch.no_grad()
 def test(args):
-    UF.set_compute_dtype(torch.bfloat16 if args.dtype == "bf16" else torch.float32)
-    model, tokenizer = prepare_model(args)
-    prompts = json.load(open(args.prompts_json)) if args.prompts_json else ensemble_for(args.dataset)
-    text_feats = class_text_features(model, tokenizer, prompts, args.device)
-    proto_sim = float(text_feats["benign"].mean(0) @ text_feats["malignant"].mean(0))
-    if proto_sim > 0.95:
-        logging.warning(f"Text prompts very similar: {proto_sim:.4f}")
-    all_logits, all_labels = [], []
-    for images, labels in _test_batches(args):
-        all_logits.append(ensemble_logits(model, images.to(args.device), text_feats).float().cpu())
-        all_labels.append(labels)
-    logits, labels = torch.cat(all_logits), torch.cat(all_labels)
-    stats = {"acc": float((logits.argmax(1) == labels).float().mean()),
-             "auc": binary_auc(torch.softmax(logits, dim=1)[:, 1], labels),
-             "loss": float(torch.nn.functional.cross_entropy(logits, labels)),
-             "n": int(len(labels))}
-    logging.info(f"zero-shot {args.dataset}: acc {stats['acc'] * 100:.2f}  auc {stats['auc']:.4f}  loss {stats['loss']:.4f}  (n={stats['n']})")
-    return stats, logits
+    """-> (stats: acc / rec / pre / f1 / auc / loss / n, logits [N, 2] on the host)."""
+    stats, logits, _ = ZS.run(args, "biomedclip", prepare_model)
+    return stats, logits.cpu()
 
 
 def main(argv=None):
-    args = get_args(argv)
-    torch.manual_seed(args.seed)
-    args.test_snapshot_path = f"runs/{args.exp}/{args.dataset}/test"
-    os.makedirs(args.test_snapshot_path, exist_ok=True)
-    setup_logging(args, args.test_snapshot_path)
-    stats, _ = test(args)
-    with open(os.path.join(args.test_snapshot_path, "results.json"), "w") as f:
-        json.dump(stats, f)
-    return stats
+    return ZS.main(get_args(argv), "biomedclip", prepare_model)
 
 
 if __name__ == "__main__":

@@ -8,7 +8,8 @@ src/third_party/openai_clip/model.py (sequence-first blocks, nn.MultiheadAttenti
 
 Differences forced by the build image: `clip.load` (torchvision transforms, the BPE vocabulary file) is not available — --ckpt is read as an OpenAI TorchScript archive or a
 plain state dict when the file exists, otherwise the ViT-B/16 geometry is randomly initialised; captions are tokenised by the deterministic stand-in tokenizer (context 77,
-<start>/<end> ids of the CLIP vocabulary).  Added, non-breaking: --dtype, --synthetic / --data_pt, --model_config, data parallelism under torch.distributed.run."""
+<start>/<end> ids of the CLIP vocabulary).  Added, non-breaking: --dtype, --synthetic / --data_pt, --model_config, data parallelism under torch.distributed.run, and --zero_shot_eval (the reference's
+run_zero_shot_evaluation, :239, opt-in here: src/models/clip/zero_shot.py once per dataset, each a fresh child process)."""
 import argparse
 import os
 import random
@@ -57,6 +58,7 @@ def get_args(argv=None):
     p.add_argument("--synthetic_val", type=int, default=128)
     p.add_argument("--data_pt", type=str, default=None)
     p.add_argument("--model_config", type=str, default=None, help="python literal: positional arguments of src.third_party.openai_clip.model.CLIP (tests)")
+    _loop.add_zero_shot_flags(p)
     return p.parse_args(argv)
 
 
@@ -95,7 +97,10 @@ def main(argv=None):
     args.train_snapshot_path = f"runs/{args.exp}"
     os.makedirs(args.train_snapshot_path, exist_ok=True)
     setup_logging(args, args.train_snapshot_path)
-    return train(args)
+    out = train(args)
+    if args.zero_shot_eval:
+        out["zero_shot"] = _loop.run_zero_shot_evaluation(args, script=Path(__file__).parent / "zero_shot.py", extra=["--ckpt", args.ckpt])      # the reference passes --ckpt on too
+    return out
 
 
 if __name__ == "__main__":

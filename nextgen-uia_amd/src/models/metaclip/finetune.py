@@ -6,12 +6,14 @@ accumulation) and loop semantics (:92-218): per batch InfoNCE on L2-normalised f
 clip_grad_norm_(1.0) → AdamW → cosine LR every iteration, a validation pass per epoch in eval mode, best-val checkpoint of
 the parameters whose name contains "mona", early stopping by --patience, runs/<exp>/{log.log,best_model.pth}.
 Added, non-breaking: --dtype, --synthetic / --data_pt, --ckpt_path, --model_config, data parallelism under
-torch.distributed.run.  The post-training zero-shot subprocess (:220-268) is outside the hot path and not launched.
+torch.distributed.run, and --zero_shot_eval: the reference's post-training zero-shot evaluation (run_zero_shot_evaluation, :240-296), which the
+reference always runs, is opt-in here — rank 0 starts src/models/metaclip/zero_shot.py once per dataset, each a fresh child process.
 """
 import argparse
 import logging
 import os
 import random
+import subprocess
 import sys
 import time
 from pathlib import Path
@@ -28,6 +30,15 @@ from src.third_party.open_clip.model import SyntheticClipTokenizer, create_metac
 from src.utils.tools import default_device, model_summary, parse_config, setup_logging
 from uia_hip import functional as UF
 from uia_hip.engine import ContrastiveLoop, DevicePrefetcher, FlatAdapterOptimizer, bind_device, dist_env, init_data_parallel, sum_over_ranks
+
+
+ZERO_SHOT_DATASETS = ("LN-INT", "LN-EXT", "BUSI")               # reference :256
+
+
+def add_zero_shot_flags(p):
+    p.add_argument("--zero_shot_eval", action="store_true", help="after training, evaluate best_model.pth zero-shot on LN-INT, LN-EXT and BUSI")
+    p.add_argument("--zero_shot_data_pt", type=str, default=None, help=".pt with {'images', 'labels'}: the evaluation's --data_pt (--synthetic is passed on as it is)")
+    p.add_argument("--zero_shot_timeout", type=int, default=3600, help="seconds one evaluation may take")
 
 
 def get_args(argv=None):
@@ -61,6 +72,7 @@ def get_args(argv=None):
     p.add_argument("--data_pt", type=str, default=None)
     p.add_argument("--ckpt_path", type=str, default=None, help="open_clip state dict (.pt); random init if absent")
     p.add_argument("--model_config", type=str, default=None, help="python dict literal overriding the model geometry (tests)")
+    add_zero_shot_flags(p)
     return p.parse_args(argv)
 
 
@@ -171,6 +183,50 @@ def train(args, prepare=None, tokenizer_of=None):
     return {"best_val": best_loss, "iters": iter_num, "last_train": train_loss, "epochs": epoch_ms}
 
 
+def run_zero_shot_evaluation(args, script=None, extra=()):
+    """reference :240-296, after train() has returned (loaders closed, communicator destroyed), on rank 0: the family's zero_shot.py once per dataset
+    on best_model.pth, each a fresh child process with the reference's arguments (:264-283) plus the adapter variant and this build's data and dtype
+    flags; `extra`: the family's model flags.  A failed or timed-out child is logged and ends the loop.  -> the datasets evaluated."""
+    if dist_env()[0] != 0:
+        return []
+    logging.info("=" * 50)
+    logging.info("Starting Zero-shot Evaluation on Fine-tuned Model")
+    logging.info("=" * 50)
+    best = os.path.join(args.train_snapshot_path, "best_model.pth")
+    if not os.path.exists(best):
+        logging.error(f"Best model checkpoint not found at {best}")
+        return []
+    script = str(script or Path(__file__).parent / "zero_shot.py")
+    done = []
+    for dataset in ZERO_SHOT_DATASETS:
+        logging.info(f"\nEvaluating on {dataset} dataset...")
+        cmd = [sys.executable, script, "--exp", f"{args.exp}", "--dataset", dataset, "--img_size", str(args.img_size), "--mona_weights", best,
+               "--mona_bottleneck", str(args.mona_bottleneck), "--batch_size", "64", "--seed", str(args.seed), "--device", args.device,
+               "--mona_variant", args.mona_variant, "--dtype", args.dtype, *extra]
+        if args.synthetic:
+            cmd.append("--synthetic")
+        if args.zero_shot_data_pt:
+            cmd += ["--data_pt", args.zero_shot_data_pt]
+        if args.model_config:
+            cmd += ["--model_config", args.model_config]
+        logging.info(f"Running command: {' '.join(cmd)}")
+        try:
+            result = subprocess.run(cmd, capture_output=True, text=True, timeout=args.zero_shot_timeout)
+        except subprocess.TimeoutExpired:
+            logging.error(f"Zero-shot evaluation timed out for {dataset} after {args.zero_shot_timeout} s; the remaining datasets are not started")
+            break
+        logging.info(result.stdout)
+        if result.returncode != 0:
+            logging.error(f"Zero-shot evaluation failed for {dataset} (exit status {result.returncode}); the remaining datasets are not started")
+            logging.error(f"Error: {result.stderr}")
+            break
+        if result.stderr:
+            logging.warning(result.stderr)
+        done.append(dataset)
+    logging.info("Zero-shot Evaluation Completed")
+    return done
+
+
 def main(argv=None):
     args = get_args(argv)
     random.seed(args.seed)
@@ -179,7 +235,10 @@ def main(argv=None):
     args.train_snapshot_path = f"runs/{args.exp}"
     os.makedirs(args.train_snapshot_path, exist_ok=True)
     setup_logging(args, args.train_snapshot_path)
-    return train(args)
+    out = train(args)
+    if args.zero_shot_eval:
+        out["zero_shot"] = run_zero_shot_evaluation(args, extra=["--ckpt_path", args.ckpt_path] if args.ckpt_path else ())
+    return out
 
 
 if __name__ == "__main__":

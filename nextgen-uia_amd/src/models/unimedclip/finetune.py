@@ -10,7 +10,8 @@ measured step) with this family's model preparation (:66-108):
   * every parameter frozen, the adapters injected, parameters whose lower-cased name contains "mona" trainable, fp32 masters (:89-106).
 Differences forced by the build image: open_clip's HFTokenizer("microsoft/BiomedNLP-BiomedBERT-base-uncased-abstract", context_length=77) needs the network — captions are
 tokenised by the deterministic BERT-style stand-in (CLS 2, SEP 3, ids 1000-30000, pad 0; context 77); without a checkpoint file the tower is randomly initialised.
-Added, non-breaking: --dtype, --synthetic / --data_pt, --model_config, data parallelism under torch.distributed.run."""
+Added, non-breaking: --dtype, --synthetic / --data_pt, --model_config, data parallelism under torch.distributed.run, and --zero_shot_eval (the reference's
+run_zero_shot_evaluation, opt-in here: src/models/unimedclip/zero_shot.py once per dataset, each a fresh child process, on the --version / --ckpt trained on)."""
 import argparse
 import logging
 import os
@@ -61,6 +62,7 @@ def get_args(argv=None):
     p.add_argument("--synthetic_val", type=int, default=128)
     p.add_argument("--data_pt", type=str, default=None)
     p.add_argument("--model_config", type=str, default=None, help="python dict literal: keyword arguments of src.third_party.open_clip.model.NativeCLIP (tests)")
+    _loop.add_zero_shot_flags(p)
     return p.parse_args(argv)
 
 
@@ -108,7 +110,10 @@ def main(argv=None):
     args.train_snapshot_path = f"runs/{args.exp}"
     os.makedirs(args.train_snapshot_path, exist_ok=True)
     setup_logging(args, args.train_snapshot_path)
-    return train(args)
+    out = train(args)
+    if args.zero_shot_eval:
+        out["zero_shot"] = _loop.run_zero_shot_evaluation(args, script=Path(__file__).parent / "zero_shot.py", extra=["--version", args.version, "--ckpt", args.ckpt])
+    return out
 
 
 if __name__ == "__main__":

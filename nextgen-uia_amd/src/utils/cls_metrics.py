@@ -54,6 +54,21 @@ class ClassificationMetrics:
         out.update(auc=auc, loss=loss_v)
         return out
 
+    def roc(self):
+        """(fpr fp64, tpr fp64, thresholds fp32) of what was accumulated, device tensors: the exact curve of torchmetrics ROC(task="binary") on
+        p1 = softmax(logits)[:, 1] (`uia_binary_roc_curve`: point 0 is (0, 0, 1.0), then one point per distinct score, descending).  One host read: the
+        number of points."""
+        if not self._logits:
+            raise ValueError("ClassificationMetrics.roc: nothing accumulated")
+        from uia_hip import ops
+        logits = torch.cat(self._logits).float()
+        labels = torch.cat(self._labels).to(torch.int64)
+        count, fpr, tpr, thr = ops.binary_roc_curve(torch.softmax(logits, dim=1)[:, 1], labels)
+        n = int(count.item())
+        if n < 0:
+            raise ValueError("ClassificationMetrics.roc: labels outside {0, 1} or a NaN score")
+        return fpr[:n], tpr[:n], thr[:n]
+
 
 def report_cls_test(args, stats, saved_best, rank=0):
     """The tail of the classification entry points' test() (reference biomedclip/classification.py:329-363): the Metric / Mean table (percent, %.2f) to

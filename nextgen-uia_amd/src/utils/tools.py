@@ -143,7 +143,8 @@ def report_test(args, stats, saved_best, rank=0):
 
 
 def backup_test_run(args, tag, csv_lines, saved_best):
-    """runs/<exp>/<dataset>/test/<time>_<tag>/ with results.csv (the given lines), a copy of the checkpoint, the viz folder and the log; returns the csv path."""
+    """runs/<exp>/<dataset>/test/<time>_<tag>/ with results.csv (the given lines), a copy of the checkpoint (saved_best None: an evaluation
+    without one), the viz folder and the log; returns the csv path."""
     import datetime
     import shutil
     backup_folder = os.path.join(args.test_snapshot_path, f"{datetime.datetime.now().strftime('%Y_%m_%d_%H_%M_%S')}_{tag}")
@@ -156,7 +157,8 @@ def backup_test_run(args, tag, csv_lines, saved_best):
     with open(csv_path, "w") as f:
         f.write("".join(line + "\n" for line in csv_lines))
     logging.info(f"Results saved to: {csv_path}")
-    shutil.copy(saved_best, os.path.join(backup_folder, "best_model.pth"))
+    if saved_best is not None:
+        shutil.copy(saved_best, os.path.join(backup_folder, "best_model.pth"))
     viz_path = args.test_snapshot_path + "/viz"
     if os.path.exists(viz_path):
         shutil.move(viz_path, os.path.join(backup_folder, "viz"))

@@ -162,6 +162,9 @@ PROTOTYPES = {
     "uia_retrieval_topk_workspace_bytes": (sz, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "uia_retrieval_topk_splits": (C.c_int, [C.c_int, C.c_int]),
     "uia_retrieval_topk": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, vp, sz, vp, vp]),
+    "uia_zero_shot_score": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int64, C.c_int64, vp, vp]),
+    "uia_binary_roc_curve_workspace_bytes": (sz, [C.c_int]),
+    "uia_binary_roc_curve": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, sz, vp, vp, vp, vp]),
     "uia_augment_workspace_bytes": (sz, [C.c_int, C.c_int]),
     "uia_augment_batch": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp, vp, sz, vp, vp]),
     "uia_infonce_workspace_bytes": (sz, [C.c_int, C.c_int]),

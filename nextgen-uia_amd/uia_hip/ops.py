@@ -1736,6 +1736,52 @@ def binary_cls_stats(p1, labels):
     return rec
 
 
+def binary_roc_curve(p1, labels):
+    """p1 fp32 [N], labels int64 [N] in {0, 1} -> (count int32 [1], fpr fp64 [N+1], tpr fp64 [N+1], thr fp32 [N+1]) device tensors: the exact ROC curve as
+    torchmetrics ROC(task="binary", thresholds=None) gives it.  Point 0 is (0, 0, 1.0), then one point per distinct score, descending; the first `count`
+    entries are the curve (the caller reads count, once; -1: a label outside {0, 1} or a NaN score).  The sort is plumbing, as in binary_cls_stats."""
+    p1 = p1.reshape(-1).to(torch.float32).contiguous()
+    lab = labels.reshape(-1).to(torch.int64).contiguous()
+    assert p1.numel() == lab.numel() and p1.device == lab.device
+    perm = torch.sort(p1, stable=True).indices
+    N = p1.numel()
+    ws = torch.empty(max(lib().uia_binary_roc_curve_workspace_bytes(N), 16), device=p1.device, dtype=torch.uint8)
+    count = torch.zeros(1, device=p1.device, dtype=torch.int32)
+    fpr = torch.zeros(N + 1, device=p1.device, dtype=torch.float64)
+    tpr = torch.zeros(N + 1, device=p1.device, dtype=torch.float64)
+    thr = torch.zeros(N + 1, device=p1.device, dtype=torch.float32)
+    check(lib().uia_binary_roc_curve(_stream(), N, _p(p1), _p(lab), _p(perm), _p(ws), ws.numel(), _p(count), _p(fpr), _p(tpr), _p(thr)),
+          "uia_binary_roc_curve")
+    return count, fpr, tpr, thr
+
+
+def zero_shot_score(img, prompts, class_off, out=None, row=0, want_probs=True, want_normalized=False):
+    """img [N, E] raw image features, prompts [T, E] raw text features of every prompt, class after class (non-fp32 is converted); class_off a host
+    sequence of C + 1 ints, class c owning the prompt rows class_off[c] .. class_off[c+1]-1 -> (logits, probs, img_n).  logits[i, c] is the mean over the
+    class's prompts of 100 · <img_i / ||img_i||, prompt_t / ||prompt_t||> (no eps), bit for bit independent of the batch the row arrives in.  out: a
+    contiguous fp32 [M, C] buffer that takes the rows [row, row + N) (a whole split in one buffer); logits is then that view.  probs fp32 [N, C] (softmax)
+    unless want_probs is False, img_n fp32 [N, E] (the normalised rows) only if want_normalized; None otherwise.  Enqueued only: nothing is read back."""
+    _p(img), _p(prompts)                                          # CPU tensors are refused before anything else
+    _require(img.dim() == 2 and prompts.dim() == 2 and img.shape[1] == prompts.shape[1] and img.device == prompts.device,
+             f"zero_shot_score: img {tuple(img.shape)} and prompts {tuple(prompts.shape)} must be [N, E] and [T, E] on one device")
+    a, b = img.detach().float().contiguous(), prompts.detach().float().contiguous()
+    (N, E), T = a.shape, b.shape[0]
+    off = [int(v) for v in (class_off.tolist() if isinstance(class_off, torch.Tensor) else class_off)]
+    Cc, row = len(off) - 1, int(row)
+    _require(Cc >= 1, "zero_shot_score: class_off needs at least two entries")
+    if out is None:
+        _require(row == 0, "zero_shot_score: a row offset needs an out buffer")
+        out = torch.empty(N, Cc, device=a.device, dtype=torch.float32)
+    _dense(out, "zero_shot_score: out", _F32)
+    _require(out.dim() == 2 and out.shape[1] == Cc and out.device == a.device and 0 <= row and row + N <= out.shape[0],
+             f"zero_shot_score: out {tuple(out.shape)} cannot take rows [{row}, {row + N}) of {Cc} classes")
+    probs = torch.empty(N, Cc, device=a.device, dtype=torch.float32) if want_probs else None
+    img_n = torch.empty(N, E, device=a.device, dtype=torch.float32) if want_normalized else None
+    offs = (C.c_int32 * (Cc + 1))(*off)
+    check(lib().uia_zero_shot_score(_stream(), N, T, E, Cc, offs, _p(a), _p(b), _p(out), Cc, row, _p(probs), _p(img_n)), "uia_zero_shot_score")
+    return out[row:row + N], probs, img_n
+
+
 def surface_distances(logits, label, percentile=95.0):
     """logits [B,2,H,W] (non-fp32 is converted), label [B,1,H,W] -> (hd, asd) fp64 device tensors [B]: MONAI's percentile Hausdorff distance (symmetric) and
     average surface distance (P -> G) of the arg-max mask against label > 0, in pixels; NaN where either mask is empty.  Enqueued only: nothing is read back."""
