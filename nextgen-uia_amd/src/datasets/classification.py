@@ -58,7 +58,9 @@ def second_of(batch):
 
 
 class DataModule:
-    def __init__(self, args):
+    def __init__(self, args, rank=0, world=1):
+        """rank / world and start_workers() / shutdown() are the segmentation DataModule's interface (src/models/supervised.py drives both): a split is
+        loaded in this process whole, so there is no shard and nothing to fork or stop."""
         self.args = args
         if getattr(args, "data_pt", None):
             blob = torch.load(args.data_pt)
@@ -90,3 +92,9 @@ class DataModule:
 
     def test_dataloader(self):
         return self._loader(self.test_dataset, False)
+
+    def start_workers(self):
+        pass
+
+    def shutdown(self):
+        pass

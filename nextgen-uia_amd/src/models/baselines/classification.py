@@ -24,8 +24,7 @@ sys.path.insert(0, str(Path(__file__).resolve().parents[3]))
 
 import torch
 
-from src.models.biomedclip import classification as _loop
-from src.models.biomedclip.classification import add_build_args
+from src.models import supervised
 from src.third_party import resnet
 from src.utils.tools import default_device
 
@@ -52,7 +51,7 @@ def get_args(argv=None):
     p.add_argument("--device", type=str, default=default_device())
     p.add_argument("--patience", type=int, default=15, help="Early stopping patience (10 * N epochs)")
     p.add_argument("--test", default=False, action="store_true", help="Load local checkpoint for testing")
-    add_build_args(p)
+    supervised.add_build_args(p)
     return p.parse_args(argv)
 
 
@@ -87,7 +86,7 @@ def prepare_model(args):
 def main(argv=None):
     args = get_args(argv)
     check_args(args)
-    return _loop.run(args, prepare_model)
+    return supervised.run(args, supervised.CLASSIFICATION, prepare_model)
 
 
 if __name__ == "__main__":

@@ -6,24 +6,20 @@ per iteration to --lr_min, no clipping), prepare_model = UNet(args.in_channels, 
 iteration, validation every 10 epochs and at the last one with best-by-Dice, early stopping by --patience, a test pass after each validation,
 the checkpoint `model.state_dict()` (BatchNorm buffers included) under runs/<exp>/<dataset>/train, and the Dice / IoU / HD95 / ASD table with
 results.csv under runs/<exp>/<dataset>/test.
-The loop is the BiomedCLIP segmentation entry point's (engine.segmentation_step, FlatAdapterOptimizer(max_norm=0) over all parameters) with
+The loop is src/models/supervised.py (engine.segmentation_step, FlatAdapterOptimizer(max_norm=0) over all parameters) with
 this model's checkpoint hooks; the model trains in train mode (batch statistics, dropout) and is evaluated in eval mode.  A one-channel batch
 is widened on the device by the model.  Refused before anything is allocated: an img_size that is not a multiple of 16 (the reference fails in
 torch.cat there).  Build additions (add_build_args): --dtype, --synthetic*, --data_pt, --stats_json, --val_every.
 """
 import argparse
-import os
-import random
 import sys
 from pathlib import Path
 
 sys.path.insert(0, str(Path(__file__).resolve().parents[3]))
 
-import numpy as np
 import torch
 
-from src.models.biomedclip import segmentation as _loop
-from src.models.biomedclip.classification import add_build_args
+from src.models import supervised
 from src.third_party.unet import UNet
 from src.utils.tools import default_device
 
@@ -49,7 +45,7 @@ def get_args(argv=None):
     p.add_argument("--device", type=str, default=default_device())
     p.add_argument("--patience", type=int, default=15, help="Early stopping patience (10 * N epochs)")
     p.add_argument("--test", default=False, action="store_true", help="Load local checkpoint for testing")
-    add_build_args(p)
+    supervised.add_build_args(p)
     return p.parse_args(argv)
 
 
@@ -68,20 +64,7 @@ def prepare_model(args):
 def main(argv=None):
     args = get_args(argv)
     check_args(args)
-    random.seed(args.seed)
-    np.random.seed(args.seed)
-    torch.manual_seed(args.seed)
-    args.train_snapshot_path = f"runs/{args.exp}/{args.dataset}/train"
-    args.test_snapshot_path = f"runs/{args.exp}/{args.dataset}/test"
-    for path in (args.train_snapshot_path, args.test_snapshot_path):
-        os.makedirs(path, exist_ok=True)
-    out = {}
-    if not args.test:
-        _loop.setup_logging(args, args.train_snapshot_path)
-        out = _loop.train(args, prepare_model)
-    _loop.setup_logging(args, args.test_snapshot_path)
-    out["test"] = _loop.test(args, prepare_model)
-    return out
+    return supervised.run(args, supervised.SEGMENTATION, prepare_model)
 
 
 if __name__ == "__main__":

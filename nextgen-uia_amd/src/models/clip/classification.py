@@ -3,7 +3,7 @@
 Its command line (:29-71: --version ViT-B/16, --ckpt ckpt/ViT-B-16.pt, default --mona_variant freq_enhanced, 1000 epochs, no LoRA flags) and model
 preparation (:78-147: CLIP from --ckpt; a --mona_weights checkpoint whose "adapter_type" is "lora" injects LoRA (its r / alpha / dropout from the checkpoint),
 any other injects Mona, both loaded by name; CLIPAdapter(task="cls") on layers 3/6/9 — pool -> Linear -> ReLU -> Dropout(0.1) -> Linear — and
-freeze_clip_backbone()); the loop is the BiomedCLIP entry point's (src/models/biomedclip/classification.py).  Without a checkpoint file the tower is a
+freeze_clip_backbone()); the loop is src/models/supervised.py.  Without a checkpoint file the tower is a
 randomly initialised CLIP of the --model_config geometry (src/models/clip/finetune.py); --ckpt_path, when given, takes the place of --ckpt."""
 import argparse
 import logging
@@ -15,7 +15,7 @@ sys.path.insert(0, str(Path(__file__).resolve().parents[3]))
 import torch
 
 from src.adapters import inject_lora_to_clip, inject_mona_variant_to_clip
-from src.models.biomedclip import classification as _loop
+from src.models import supervised
 from src.models.biomedclip.zero_shot import load_adapter_by_name
 from src.models.clip.finetune import _geometry
 from src.third_party.openai_clip.clip_adapter import CLIPAdapter
@@ -52,7 +52,7 @@ def get_args(argv=None):
     p.add_argument("--device", type=str, default=default_device())
     p.add_argument("--patience", type=int, default=15)
     p.add_argument("--test", default=False, action="store_true")
-    _loop.add_build_args(p)
+    supervised.add_build_args(p)
     return p.parse_args(argv)
 
 
@@ -71,7 +71,7 @@ def prepare_model(args):
             inject_mona_variant_to_clip(clip_model, variant=args.mona_variant, bottleneck_dim=args.mona_bottleneck, num_layers=args.mona_layers)
             n = load_adapter_by_name(clip_model, args.mona_weights, "mona_state_dict")
             logging.info(f"✓ Loaded {n} pretrained MONA parameters from {args.mona_weights}")
-    adapter = CLIPAdapter(clip_model=clip_model, extract_layers=_loop.extract_layers(args), reduce_dim=args.reduce_dim, num_classes=args.num_classes,
+    adapter = CLIPAdapter(clip_model=clip_model, extract_layers=supervised.extract_layers(args), reduce_dim=args.reduce_dim, num_classes=args.num_classes,
                           img_size=args.img_size, patch_size=args.patch_size, task="cls")
     adapter.to(args.device)
     adapter.freeze_clip_backbone()
@@ -79,7 +79,7 @@ def prepare_model(args):
 
 
 def main(argv=None):
-    return _loop.run(get_args(argv), prepare_model)
+    return supervised.run(get_args(argv), supervised.CLASSIFICATION, prepare_model)
 
 
 if __name__ == "__main__":

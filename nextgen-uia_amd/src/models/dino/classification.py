@@ -6,7 +6,7 @@ ckpt/dinov2_vitb14_pretrain.pth loaded through load_pretrained_weights with chec
 eval mode; ClassificationHead(768, num_classes, layers=4)), and the loop (:90-235): FocalLoss(to_onehot_y=True), AdamW over the classifier only,
 validation at `epoch > 0 and epoch % 10 == 0` and at the last epoch, best-by-accuracy `classifier.state_dict()` in best_model.pth, early stopping by
 --patience, a test-split pass after every validation, and test() with the Acc / Rec / Pre / F1 / AUC table, results.csv and the backup folder.
-The loop is the BiomedCLIP entry point's (src/models/biomedclip/classification.py) with this model's checkpoint hooks.
+The loop is src/models/supervised.py with this model's checkpoint hooks.
 Build additions (add_build_args): --dtype, --synthetic*, --data_pt, --ckpt_path (a DINOv2 checkpoint in place of the default path), --stats_json,
 --val_every.  Without a checkpoint the tower is randomly initialised (logged).
 """
@@ -21,7 +21,7 @@ sys.path.insert(0, str(Path(__file__).resolve().parents[3]))
 import torch
 import torch.nn as nn
 
-from src.models.biomedclip import classification as _loop
+from src.models import supervised
 from src.third_party.dino import vision_transformer as vit
 from src.third_party.dino.dinov2 import ClassificationHead, DINOV2Encoder, load_pretrained_weights
 from src.utils.tools import default_device
@@ -51,7 +51,7 @@ def get_args(argv=None):
     p.add_argument("--device", type=str, default=default_device())
     p.add_argument("--patience", type=int, default=15, help="Early stopping patience (10 * N epochs)")
     p.add_argument("--test", default=False, action="store_true", help="Load local checkpoint for testing")
-    _loop.add_build_args(p)
+    supervised.add_build_args(p)
     return p.parse_args(argv)
 
 
@@ -100,7 +100,7 @@ def prepare_model(args):
 
 
 def main(argv=None):
-    return _loop.run(get_args(argv), prepare_model)
+    return supervised.run(get_args(argv), supervised.CLASSIFICATION, prepare_model)
 
 
 if __name__ == "__main__":

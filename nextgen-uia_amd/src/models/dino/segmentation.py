@@ -6,7 +6,7 @@ ckpt/dinov2_vitb14_pretrain.pth with checkpoint key "student" when it exists, th
 num_classes, "unet", img_size, patch_size)), DiceCE per iteration, validation every 10 epochs and at the last one with best-by-Dice, early stopping
 by --patience, a test pass after each validation, the checkpoint `decoders.state_dict()` (BatchNorm buffers included) loaded with strict=False by
 test(), and the Dice / IoU / HD95 / ASD table with results.csv.
-The loop is the BiomedCLIP segmentation entry point's (engine.segmentation_step, FlatAdapterOptimizer(max_norm=0) over the decoder parameters) with
+The loop is src/models/supervised.py (engine.segmentation_step, FlatAdapterOptimizer(max_norm=0) over the decoder parameters) with
 this model's checkpoint hooks; the decoder trains in train mode and is evaluated in eval mode.  A one-channel batch goes through the tower's
 channel-summed patch embedding.  Refused before anything is allocated: a decoder_type other than unet (the reference's linear decoder fails on its own
 encoder output) and an img_size that is not a multiple of patch_size.  Build additions (add_build_args): --dtype, --synthetic*, --data_pt, --ckpt_path,
@@ -15,18 +15,15 @@ encoder output) and an img_size that is not a multiple of patch_size.  Build add
 import argparse
 import logging
 import os
-import random
 import sys
 from pathlib import Path
 
 sys.path.insert(0, str(Path(__file__).resolve().parents[3]))
 
-import numpy as np
 import torch
 import torch.nn as nn
 
-from src.models.biomedclip import segmentation as _loop
-from src.models.biomedclip.classification import add_build_args
+from src.models import supervised
 from src.third_party.dino import vision_transformer as vit
 from src.third_party.dino.dinov2 import DINOV2Encoder, load_pretrained_weights, setup_decoders
 from src.utils.tools import default_device
@@ -57,7 +54,7 @@ def get_args(argv=None):
     p.add_argument("--device", type=str, default=default_device())
     p.add_argument("--patience", type=int, default=15, help="Early stopping patience (10 * N epochs)")
     p.add_argument("--test", default=False, action="store_true", help="Load local checkpoint for testing")
-    add_build_args(p)
+    supervised.add_build_args(p)
     return p.parse_args(argv)
 
 
@@ -118,20 +115,7 @@ def prepare_model(args):
 def main(argv=None):
     args = get_args(argv)
     check_args(args)
-    random.seed(args.seed)
-    np.random.seed(args.seed)
-    torch.manual_seed(args.seed)
-    args.train_snapshot_path = f"runs/{args.exp}/{args.dataset}/train"
-    args.test_snapshot_path = f"runs/{args.exp}/{args.dataset}/test"
-    for path in (args.train_snapshot_path, args.test_snapshot_path):
-        os.makedirs(path, exist_ok=True)
-    out = {}
-    if not args.test:
-        _loop.setup_logging(args, args.train_snapshot_path)
-        out = _loop.train(args, prepare_model)
-    _loop.setup_logging(args, args.test_snapshot_path)
-    out["test"] = _loop.test(args, prepare_model)
-    return out
+    return supervised.run(args, supervised.SEGMENTATION, prepare_model)
 
 
 if __name__ == "__main__":

@@ -2,8 +2,8 @@
 
 Its command line (:29-70: --version ViT-B-16-quickgelu, --ckpt ckpt/unimed_clip_vit_b16.pt, default --mona_variant noise_aware, 1000 epochs, no LoRA flags)
 and model preparation (:76-140: open_clip's NATIVE tower with QuickGELU forced, the checkpoint's `visual.*` keys and `logit_scale` loaded strict=False,
-optional Mona adapters loaded by name, TimmCLIPAdapter(task="cls") on layers 3/6/9, freeze_clip_backbone()); the loop is the BiomedCLIP entry point's
-(src/models/biomedclip/classification.py).  The native tower has `visual.transformer` with batch-first blocks: the adapter feeds them the batch-first
+optional Mona adapters loaded by name, TimmCLIPAdapter(task="cls") on layers 3/6/9, freeze_clip_backbone()); the loop is that of
+src/models/supervised.py.  The native tower has `visual.transformer` with batch-first blocks: the adapter feeds them the batch-first
 tokens as they are (classification, note C-cls-1).  --ckpt_path, when given, takes the place of --ckpt."""
 import argparse
 import logging
@@ -16,7 +16,7 @@ sys.path.insert(0, str(Path(__file__).resolve().parents[3]))
 import torch
 
 from src.adapters import inject_mona_variant_to_open_clip
-from src.models.biomedclip import classification as _loop
+from src.models import supervised
 from src.models.biomedclip.zero_shot import load_adapter_by_name
 from src.third_party.open_clip.model import create_native_clip
 from src.third_party.timm.clip_adapter import TimmCLIPAdapter
@@ -52,7 +52,7 @@ def get_args(argv=None):
     p.add_argument("--device", type=str, default=default_device())
     p.add_argument("--patience", type=int, default=15)
     p.add_argument("--test", default=False, action="store_true")
-    _loop.add_build_args(p)
+    supervised.add_build_args(p)
     return p.parse_args(argv)
 
 
@@ -75,7 +75,7 @@ def prepare_model(args):
         inject_mona_variant_to_open_clip(clip_model, variant=args.mona_variant, bottleneck_dim=args.mona_bottleneck, num_layers=args.mona_layers)
         n = load_adapter_by_name(clip_model, args.mona_weights, "mona_state_dict")
         logging.info(f"✓ Loaded {n} pretrained MONA parameters from {args.mona_weights}")
-    adapter = TimmCLIPAdapter(clip_model=clip_model, extract_layers=_loop.extract_layers(args), reduce_dim=args.reduce_dim, num_classes=args.num_classes,
+    adapter = TimmCLIPAdapter(clip_model=clip_model, extract_layers=supervised.extract_layers(args), reduce_dim=args.reduce_dim, num_classes=args.num_classes,
                               img_size=args.img_size, patch_size=args.patch_size, task="cls")
     adapter.to(args.device)
     adapter.freeze_clip_backbone()
@@ -83,7 +83,7 @@ def prepare_model(args):
 
 
 def main(argv=None):
-    return _loop.run(get_args(argv), prepare_model)
+    return supervised.run(get_args(argv), supervised.CLASSIFICATION, prepare_model)
 
 
 if __name__ == "__main__":

@@ -418,6 +418,46 @@ def test_other_classification_clis_run_at_toy_geometry(tmp_path, monkeypatch, fa
     assert math.isfinite(out["last_loss"]) and math.isfinite(out["test"]["loss"]) and os.path.exists(out["test"]["results_csv"])
 
 
+# ------------------------------------------------------------------------------------------------ early stopping
+ZERO_STEP = ["--synthetic_train", "16", "--epochs", "6", "--val_every", "1", "--patience", "1", "--lr", "0", "--lr_min", "0"]      # two batches of 8 per epoch
+
+
+def test_classification_stops_early_when_patience_runs_out(tmp_path, monkeypatch):
+    """At a learning rate of 0 (AdamW: p <- p·(1 - lr·wd) - lr·m/(sqrt(v) + eps), so no parameter moves) every validation returns the first one's figures.
+    Validations follow epochs 1, 2, ... (`epoch > 0`).  A first accuracy v > 0 is the best so far, the second one is no strict improvement: patience 1 is
+    used up after three epochs.  v == 0 never beats the initial 0.0: the loop stops after two epochs and best_model.pth is the last iterate."""
+    from src.models.biomedclip import classification as cli
+    monkeypatch.chdir(tmp_path)
+    argv = BIOMED + ZERO_STEP + ["--exp", "es", "--dataset", "SYN"]
+    out = cli.main(argv)
+    accs = [h["acc"] for h in out["val"]]
+    validations = 2 if accs[0] > 0 else 1
+    print(f"early stop: val acc {accs}, iters {out['iters']}, best {out['best_val_acc']}")
+    assert len(accs) == validations and all(a == accs[0] for a in accs), accs
+    assert out["iters"] == (validations + 1) * 2 and out["best_val_acc"] == accs[0]
+    assert "test" in out["val"][0] if validations == 2 else "test" not in out["val"][0]      # the stopping validation has no test pass behind it
+    assert os.path.exists("runs/es/SYN/train/best_model.pth")
+    again = cli.main(argv + ["--test"])["test"]
+    for k in ("acc", "auc", "loss"):
+        assert abs(again[k] - out["test"][k]) <= 1e-6, (k, again[k], out["test"][k])
+
+
+def test_segmentation_stops_early_when_patience_runs_out(tmp_path, monkeypatch):
+    """The same bookkeeping in the BiomedCLIP segmentation entry point (the toy geometry of tests/test_parity_gpu.py); its dict has no validation
+    history, so the number of validations follows from the best Dice it reports: above 0 two of them, else one."""
+    from src.models.biomedclip import segmentation
+    monkeypatch.chdir(tmp_path)
+    cfg = ("dict(embed_dim=128, vision_cfg=dict(img_size=32, patch_size=8, embed_dim=128, depth=3, num_heads=2), "
+           "text_cfg=dict(vocab_size=30000, hidden_size=128, num_hidden_layers=1, num_attention_heads=2, intermediate_size=256, max_position_embeddings=64))")
+    out = segmentation.main(["--synthetic", "--synthetic_val", "16", "--synthetic_test", "16", "--img_size", "32", "--patch_size", "8", "--batch_size", "8",
+                             "--reduce_dim", "64", "--extract_layers", "0,1,2", "--dtype", "bf16", "--exp", "es", "--model_config", cfg, "--num_workers", "0"]
+                            + ZERO_STEP)
+    validations = 2 if out["best_val_dice"] > 0 else 1
+    print(f"early stop: best val dice {out['best_val_dice']}, iters {out['iters']}")
+    assert out["iters"] == (validations + 1) * 2
+    assert os.path.exists("runs/es/LN-INT/train/best_model.pth") and math.isfinite(out["test"]["loss"])
+
+
 # ------------------------------------------------------------------------------------------------ descent
 DESCENT_ACC_BAR = 0.90            # measured on the MI355X: 0.969 in each of three runs (0.844 after 10 epochs)
 DESCENT_LOSS_BAR = 0.150           # measured 0.1341-0.1342 (0.169 after 10 epochs; chance 0.1733)

@@ -665,7 +665,7 @@ def test_biomedclip_segmentation_entry_point(tmp_path, monkeypatch):
     assert saved.exists()        # reference: saved when the validation Dice improves on 0; round 6: otherwise the last iterate, so that the test pass main() always runs has a checkpoint
     args = segmentation.get_args(["--synthetic", "--img_size", "32", "--patch_size", "8", "--reduce_dim", "64", "--extract_layers", "0,1,2",
                                   "--mona_weights", str(tmp_path / "runs" / "ft" / "best_model.pth"), "--model_config", cfg])
-    ck = segmentation.checkpoint_dict(segmentation.prepare_model(args))
+    ck = segmentation.prepare_model(args).checkpoint_dict()
     assert set(ck) == {"reduces", "blocks", "seg_head", "mona"} and "1.weight" in ck["seg_head"] and "0.weight" in ck["reduces"]
     assert ck["mona"] and all("mona" in k for k in ck["mona"])
 

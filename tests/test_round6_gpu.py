@@ -72,18 +72,19 @@ def test_clipseg_cli_as_a_child_process(tmp_path):
 def test_clipseg_entry_point_in_process_train_then_test_only(tmp_path, monkeypatch):
     """main() without --test trains and tests; main(--test) afterwards loads runs/<exp>/<dataset>/train/best_model.pth and reports the same test metrics (the
     checkpoint round trip through {"decoder": state_dict}, reference :238-248); betas come from --beta1 / --beta2; an unknown dataset has no prompt."""
+    from src.models import supervised
     from src.models.clipseg import segmentation as S
     monkeypatch.chdir(tmp_path)
     common = ["--dataset", "BUSI", "--synthetic", "--synthetic_train", "16", "--synthetic_val", "8", "--synthetic_test", "8", "--img_size", "64", "--batch_size", "8",
               "--dtype", "fp32", "--exp", "t", "--num_workers", "0"]
     seen = {}
-    real = S.FlatAdapterOptimizer
+    real = supervised.FlatAdapterOptimizer
 
     class Spy(real):
         def __init__(self, named, **kw):
             seen.update(kw)
             super().__init__(named, **kw)
-    monkeypatch.setattr(S, "FlatAdapterOptimizer", Spy)
+    monkeypatch.setattr(supervised, "FlatAdapterOptimizer", Spy)
     out = S.main(common + ["--epochs", "2", "--lr", "1e-3", "--beta1", "0.8", "--beta2", "0.9"])
     assert seen["betas"] == (0.8, 0.9) and seen["max_norm"] == 0.0 and seen["weight_decay"] == 0.01
     assert out["train"]["iters"] == 4 and math.isfinite(out["test"]["loss"]) and 0.0 <= out["test"]["iou_mean"] <= out["test"]["dice_mean"] <= 1.0

@@ -214,6 +214,7 @@ def test_update_does_not_synchronise_with_the_host():
 def test_clipseg_test_pass_reports_the_restated_hd95_and_asd(tmp_path, monkeypatch):
     """The CLIPSeg entry point in process (the tiny synthetic configuration of tests/test_round6_gpu.py): test()'s statistics equal the restatement on what
     its accumulator received, and results.csv carries them."""
+    from src.models import supervised
     from src.models.clipseg import segmentation as S
     from src.utils.tools import MetricAccumulator
     monkeypatch.chdir(tmp_path)
@@ -232,7 +233,7 @@ def test_clipseg_test_pass_reports_the_restated_hd95_and_asd(tmp_path, monkeypat
         def update(self, preds, labels):
             self.passes[-1].append((preds.detach().float().cpu().clone(), labels.detach().float().cpu().clone()))
             super().update(preds, labels)
-    monkeypatch.setattr(S, "MetricAccumulator", Spy)
+    monkeypatch.setattr(supervised, "MetricAccumulator", Spy)
     out = S.main(["--dataset", "BUSI", "--synthetic", "--synthetic_train", "16", "--synthetic_val", "8", "--synthetic_test", "8", "--img_size", "64",
                   "--batch_size", "8", "--dtype", "fp32", "--exp", "t", "--num_workers", "0", "--epochs", "2", "--lr", "1e-3"])
     seen = made[-1].passes[-2]                                   # test()'s accumulator is created last; its pass is the one before the final reset()

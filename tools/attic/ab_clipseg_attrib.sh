@@ -1,4 +1,5 @@
 #!/bin/bash
+# ATTIC: last ran against commit 7a0abad; it needs the UIA_SEG_AB knobs and src/models/clipseg/_measure.py, which left the package with the next commit (findings: DESIGN.md §4, round 6 item 1).
 # Which ingredient of the CLIPSeg CLI's epoch loop costs GPU time against bench.py's resident-batch loop?  UIA_SEG_AB=attrib runs the resident loop in the CLI's process with one ingredient
 # added at a time (host-to-device copies on a side stream, the wait on their event, the step reading rotating buffers, an event record per step).
 cd $GRAFT_REPO_ROOT

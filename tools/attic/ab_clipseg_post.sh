@@ -1,4 +1,5 @@
 #!/bin/bash
+# ATTIC: last ran against commit 7a0abad; it needs the UIA_SEG_AB knobs and src/models/clipseg/_measure.py, which left the package with the next commit (findings: DESIGN.md §4, round 6 item 1).
 # Is it the CLI's LOOP or the CLI's PROCESS that runs the CLIPSeg step 4 % slower than bench.py?  UIA_SEG_AB=post times bench.py's loop (resident batch, 120 steps) inside the CLI's process after
 # its loaders are shut down; alternated with the CLI's own epochs and with bench.py on the same box.
 cd $GRAFT_REPO_ROOT

@@ -6,7 +6,7 @@ baseline loop with the stage bypassed, on, and on with an all-empty program tabl
           every image, every opcode among them, two crops).  HIP events around one call (table copy + kernel); the median of --reps calls after --warmup,
           five times over; the median of the five medians.
   step:   UNet(3, 2) in train mode, DiceCE, FlatAdapterOptimizer over all parameters, engine.segmentation_step on a resident [32, 1, 224, 224] batch — the
-          loop body of src/models/biomedclip/segmentation.train — with `bypass` (stage_for(...) is None: what --no-strong_augs --no-weak_augs and --synthetic
+          loop body of src/models/supervised.train — with `bypass` (stage_for(...) is None: what --no-strong_augs --no-weak_augs and --synthetic
           run), `on` (BatchAugmenter with both flags) and `empty` (BatchAugmenter with no flag: it draws, copies and launches, every program empty).  HIP
           events around each step, nothing synchronised inside a round of --steps steps; the median step of a round, five rounds, the median and the spread
           (min .. max) of the five medians.  The stage adds no host synchronisation when `empty` lies within the spread of `bypass`.
