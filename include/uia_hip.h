@@ -465,6 +465,25 @@ int uia_binary_cls_stats(void* stream, int N, const float* p1, const int64_t* la
 size_t uia_surface_distances_workspace_bytes(int B, int H, int W);
 int uia_surface_distances(void* stream, int B, int H, int W, const float* logits, const float* label, float percentile, void* ws, size_t ws_bytes,
                           double* hd, double* asd);
+/* The three pictures of the segmentation test pass (reference src/utils/tools.py:278-315, visualize_seg: `(images * 255).astype(np.uint8)`,
+ * `torch.argmax(preds, dim=1)`, the np.maximum overlays, one image at a time on the host), for a whole batch in one launch.
+ * logits fp32 [B,C,S,S] with C == 2, contiguous; images fp32 [B,Ci,S,S] with Ci 1 or 3, of which channel 0 is read; labels [B,1,S,S] as uint8
+ * (label_dtype UIA_SEG_LABEL_U8) or fp32 (UIA_SEG_LABEL_F32); B >= 1, 1 <= S <= 16384, B*S*S <= 2^36; fp32 inputs on 4-byte addresses.
+ * Per pixel: g = (uint8)(x * 255), the product rounded once to fp32, clamped to [0, 255] with NaN -> 0 (numpy leaves out-of-range values undefined), then
+ * truncated; t = 255 where label != 0, else 0; p = 255 where argmax over the two logits is class 1 by torch's rules (a tie, -0.0 against +0.0 included,
+ * goes to class 0; NaN is the maximum; NaN in both goes to class 0), the prediction uia_surface_distances and the Dice / IoU metrics use, else 0.
+ * Outputs, caller-owned uint8, plain row-major with no PNG filter bytes: mask_rgb [B,S,S,3] = (t, p, 0), overlay_rgb [B,S,S,3] =
+ * (max(g,t), max(g,p), g), pred [B,S,S] = p.  Every byte of the three is written, nothing beside them.
+ * Everything is checked before anything is enqueued (non-zero, uia_last_error(), nothing written): null pointers, B or S out of range, C != 2,
+ * Ci not 1 or 3, an unknown label_dtype, an output that overlaps another output or an input.  Asynchronous, deterministic, no workspace.
+ * uia_seg_viz_form: 1 when the call runs on the four-pixels-per-thread kernel (16-byte loads, dword stores): S % 4 == 0, logits, images and fp32
+ * labels on 16-byte addresses, uint8 labels and the three outputs on 4-byte addresses; 0 for the pixel-per-thread kernel with byte stores that takes
+ * everything else.  A pure function of its arguments: no GPU is needed. */
+enum { UIA_SEG_LABEL_U8 = 0, UIA_SEG_LABEL_F32 = 1 };
+int uia_seg_viz_form(int S, int label_dtype, const void* logits, const void* images, const void* labels, const void* mask_rgb, const void* overlay_rgb,
+                     const void* pred);
+int uia_seg_viz(void* stream, int B, int C, int Ci, int S, const float* logits, const float* images, const void* labels, int label_dtype,
+                uint8_t* mask_rgb, uint8_t* overlay_rgb, uint8_t* pred);
 /* Image-text retrieval evaluation (the call sites of reference src/models/biomedclip/retrieval.py:329; the reference never shipped its metric module, so
  * these definitions are this build's).  img, txt fp32 [N,E] row-major contiguous, 16-byte aligned: N feature pairs; 1 <= N <= 2^24, E % 4 == 0,
  * 4 <= E <= 4096.  Scores s_ij = <a_i, b_j> with a_i = img_i / max(||img_i||, 1e-12), b_j likewise from txt_j (F.normalize) when normalize != 0, else

@@ -241,6 +241,11 @@ int uia_surface_distances(void* stream, int B, int H, int W, const float* logits
     return uia_surface_launch((hipStream_t)stream, B, H, W, logits, label, percentile, ws, ws_bytes, hd, asd);
 }
 
+int uia_seg_viz(void* stream, int B, int C, int Ci, int S, const float* logits, const float* images, const void* labels, int label_dtype,
+                uint8_t* mask_rgb, uint8_t* overlay_rgb, uint8_t* pred) {
+    return uia_seg_viz_launch((hipStream_t)stream, B, C, Ci, S, logits, images, labels, label_dtype, mask_rgb, overlay_rgb, pred);
+}
+
 size_t uia_retrieval_workspace_bytes(int N, int E) { return uia_retrieval_ranks_ws_bytes(N, E); }
 int uia_retrieval_ranks(void* stream, int N, int E, const float* img, const float* txt, int normalize, void* ws, size_t ws_bytes,
                         int32_t* gt_i2t, int32_t* eq_i2t, int32_t* gt_t2i, int32_t* eq_t2i) {

@@ -91,6 +91,8 @@ int uia_binary_cls_stats_launch(hipStream_t stream, int N, const float* p1, cons
 size_t uia_surface_ws_bytes(int B, int H, int W);
 int uia_surface_launch(hipStream_t stream, int B, int H, int W, const float* logits, const float* label, float percentile, void* ws, size_t ws_bytes,
                        double* hd, double* asd);
+int uia_seg_viz_launch(hipStream_t stream, int B, int C, int Ci, int S, const float* logits, const float* images, const void* labels, int label_dtype,
+                       uint8_t* mask_rgb, uint8_t* overlay_rgb, uint8_t* pred);
 size_t uia_retrieval_ranks_ws_bytes(int N, int E);
 int uia_retrieval_ranks_launch(hipStream_t stream, int N, int E, const float* img, const float* txt, int normalize, void* ws, size_t ws_bytes,
                                int32_t* gt_i2t, int32_t* eq_i2t, int32_t* gt_t2i, int32_t* eq_t2i);

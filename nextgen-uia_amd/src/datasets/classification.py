@@ -42,6 +42,9 @@ class TensorClassification(Dataset):
     def __len__(self):
         return len(self.names)
 
+    def name_of(self, i):
+        return self.names[i]
+
     def __getitem__(self, i):
         img = self.images[i]
         img = img.float() / 255.0 if img.dtype == torch.uint8 else img.float()

@@ -89,8 +89,12 @@ class SyntheticSegmentation(Dataset):
     def __len__(self):
         return self.n
 
+    def name_of(self, i):
+        """The file name of sample i without producing the sample (the test pass names its pictures by it)."""
+        return f"{self.prefix}_{i:05d}.png"
+
     def __getitem__(self, i):
-        name = f"{self.prefix}_{i:05d}.png"
+        name = self.name_of(i)
         if self._have is not None and bool(self._have[i]):
             return self._img[i], self._lab[i], name
         img, lab = synthetic_sample(self.img_size, self.seed * 1000003 + i)
@@ -107,6 +111,9 @@ class TensorSegmentation(Dataset):
 
     def __len__(self):
         return len(self.names)
+
+    def name_of(self, i):
+        return self.names[i]
 
     def __getitem__(self, i):
         img = self.images[i]

@@ -10,7 +10,8 @@ the test pass after every validation (:259-280), `test()` (:283-355: checkpoint 
 Metric / Mean / Std table, results.csv and the backup folder) and `main` (train unless --test, then ALWAYS test).
 Different on purpose: the iteration is engine.segmentation_step with nothing read on the host, batches through engine.DevicePrefetcher (one grayscale channel +
 a uint8 mask per image, repeated on the device), --strong_augs / --weak_augs applied to --data_pt training batches on the device (src/datasets/augment.py),
-Dice / IoU on the device; MONAI's HD95 / ASD (scipy surface distances on the host) are reported as NaN and
+Dice / IoU and, for two-class logits, MONAI's HD95 / ASD on the device (uia_surface_distances), the test pass's visualize_seg pictures (three PNG
+files per test image under <test dir>/viz) from one launch per batch behind the metrics with background writers (src/utils/viz.py; --no-viz: none) and
 TensorBoard scalars go to <train dir>/log/scalars.jsonl.  Data: `--synthetic` or `--data_pt` (src/datasets/segmentation.py).
 """
 import argparse

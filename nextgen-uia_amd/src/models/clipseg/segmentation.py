@@ -86,6 +86,8 @@ def get_args(argv=None):
     parser.add_argument("--decoder_ckpt", type=str, default=None, help="CIDAS/clipseg-rd64-refined decoder state dict (the reference downloads it)")
     parser.add_argument("--val_every", type=int, default=10, help="epochs between validations (reference: fixed 10)")
     parser.add_argument("--stats_json", type=str, default=None, help="write per-epoch timings / counters of the training loop here")
+    parser.add_argument("--viz", default=True, action=argparse.BooleanOptionalAction,
+                        help="test(): write <stem>.png / <stem>_overlay.png / <stem>_pred.png per test image (reference: always)")
     return parser.parse_args(argv)
 
 

@@ -4,7 +4,8 @@ shared flags (`add_build_args`) and the two task descriptions the loop reads (`C
 What the reference repeats per family (src/models/*/classification.py, src/models/*/segmentation.py): FocalLoss / DiceCE per iteration, AdamW with a
 per-iteration cosine schedule and no clipping, validation at `epoch > 0 and epoch % 10 == 0` and at the last epoch, the best checkpoint by a strict >
 on one metric, early stopping by --patience, a test-split pass after every validation; `test()`: best_model.pth -> model -> metrics over the test split ->
-the results table, results.csv and the backup folder; `main`: train unless --test, then ALWAYS test.
+the results table, results.csv and the backup folder, and for segmentation the reference's visualize_seg pictures of every test image
+(src/utils/viz.py: one launch per batch, written by background threads; --no-viz leaves the folder empty; the test passes inside train() write none); `main`: train unless --test, then ALWAYS test.
 Different on purpose: the iteration is engine.segmentation_step (zero_grad -> forward -> criterion -> backward -> AdamW, nothing read on the host; every
 tenth loss is kept as a device scalar and written at validation time), batches arrive through engine.DevicePrefetcher, --strong_augs / --weak_augs act
 on --data_pt training batches on the device (src/datasets/augment.py), metrics are computed on the device (one host read per split), scalars go to
@@ -14,6 +15,7 @@ What differs by task is a field of `Task`; what differs by model is an argument:
 dict of extra forward keyword arguments)`, called once behind the model's preparation (CLIPSeg: its prompt).  A model says what its checkpoint holds:
 `checkpoint_dict()` and `load_checkpoint(state)`.
 """
+import argparse
 import functools
 import logging
 import os
@@ -31,6 +33,7 @@ from src.losses.dice import DiceCELoss
 from src.losses.focal import FocalLoss
 from src.utils.cls_metrics import ClassificationMetrics, report_cls_test
 from src.utils.tools import MetricAccumulator, ScalarLog, fresh_viz_dir, model_summary, report_test, setup_logging
+from src.utils.viz import SegVisualizer
 from uia_hip import functional as UF
 from uia_hip.engine import DevicePrefetcher, FlatAdapterOptimizer, bind_device, cosine_lr, dist_env, init_data_parallel, segmentation_step
 
@@ -54,6 +57,7 @@ class Task:
     lr_scalar: bool = False         # <exp>/lr beside every logged training loss
     loop_timings: bool = False      # epoch records carry loader_wait_ms / enqueue_ms / drain_ms
     stop_twice: bool = False        # the reference's second early-stopping line
+    visualize: bool = False         # test() writes the reference's three pictures per test image into <test dir>/viz (src/utils/viz.py) unless --no-viz
 
 
 def _cls_input(images, labels, in_channels, bufs=None):
@@ -77,7 +81,7 @@ CLASSIFICATION = Task(data=dataset_cls, criterion=FocalLoss(to_onehot_y=True), m
                       to_input=_cls_input, with_mask=False, data_parallel=False, val_history=True)
 SEGMENTATION = Task(data=dataset_seg, criterion=DiceCELoss(smooth_nr=1e-8, smooth_dr=1e-8), metrics=_seg_metrics, report=report_test, best="dice_mean", best_name="best_val_dice", best_words="a mean Dice", scalars=("loss", "dice_mean", "iou_mean"),
                     line=_seg_line, to_input=functools.partial(dataset_seg.as_model_input, widen=False), with_mask=True, data_parallel=True,
-                    val_history=False)
+                    val_history=False, visualize=True)
 
 
 def add_build_args(p, synthetic_train=256):
@@ -93,6 +97,8 @@ def add_build_args(p, synthetic_train=256):
     p.add_argument("--model_config", type=str, default=None)
     p.add_argument("--extract_layers", type=str, default="3,6,9", help="transformer blocks tapped by the adapter (reference: fixed 3,6,9)")
     p.add_argument("--val_every", type=int, default=10, help="epochs between validations (reference: fixed 10)")
+    p.add_argument("--viz", default=True, action=argparse.BooleanOptionalAction,
+                   help="segmentation test(): write <stem>.png / <stem>_overlay.png / <stem>_pred.png per test image (reference: always)")
 
 
 def extract_layers(args):
@@ -114,15 +120,21 @@ def _bind(args, task):
     UF.set_compute_dtype(torch.bfloat16 if args.dtype == "bf16" else torch.float32)
 
 
-def evaluate(task, model, loader_pf, accumulator, in_channels=3, kwargs_for=_no_kwargs):
-    """One pass of a validation / test split."""
+def evaluate(task, model, loader_pf, accumulator, in_channels=3, kwargs_for=_no_kwargs, viz=None, name_of=None):
+    """One pass of a validation / test split.  viz: a src.utils.viz.SegVisualizer that takes every batch behind its metrics, with name_of(i) the file
+    name of sample i of the split (the prefetcher drops names; these loaders do not shuffle, so a running index is the sample's)."""
     cur = torch.cuda.current_stream()
     to_input = task.to_input
+    seen = 0
     with torch.no_grad():
         for images, labels, ready in loader_pf:
             cur.wait_event(ready)
             images, labels = to_input(images, labels, in_channels)
-            accumulator.update(model(images, **kwargs_for(images.shape[0])).detach(), labels.detach())
+            preds = model(images, **kwargs_for(images.shape[0])).detach()
+            accumulator.update(preds, labels.detach())
+            if viz is not None:
+                viz.submit(images, labels, preds, [name_of(seen + j) for j in range(images.shape[0])])
+                seen += images.shape[0]
 
 
 def _split_pass(task, model, loader_pf, accumulator, args, kwargs_for, writer, split, iter_num):
@@ -265,12 +277,19 @@ def test(args, task, prepare, forward_kwargs=None):
     UF.WEIGHTS.bump()
     model.eval()
     kwargs_for = forward_kwargs(args) if forward_kwargs is not None else _no_kwargs
+    viz = None
     if rank == 0:
-        fresh_viz_dir(args)
+        viz_path = fresh_viz_dir(args)
+        if task.visualize and getattr(args, "viz", True):
+            viz = SegVisualizer(viz_path, args.batch_size, args.img_size)
     accumulator = task.metrics(criterion=task.criterion, num_classes=args.num_classes)
     test_pf = DevicePrefetcher(testloader, None, args.device, second=task.data.second_of)
-    evaluate(task, model, test_pf, accumulator, args.in_channels, kwargs_for)
-    stats = accumulator.compute()
+    try:
+        evaluate(task, model, test_pf, accumulator, args.in_channels, kwargs_for, viz, dm.test_dataset.name_of)
+        stats = accumulator.compute()
+    finally:
+        if viz is not None:
+            viz.close()                                          # the last files are on disk before the folder moves; a writer's exception surfaces here
     accumulator.reset()
     test_pf.close()
     dm.shutdown()

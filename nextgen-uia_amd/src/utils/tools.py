@@ -169,10 +169,30 @@ def backup_test_run(args, tag, csv_lines, saved_best):
 
 
 def fresh_viz_dir(args):
-    """runs/<exp>/<dataset>/test/viz, emptied (reference clipseg/segmentation.py:256-260); visualize_seg's matplotlib overlays themselves are outside this build."""
+    """runs/<exp>/<dataset>/test/viz, emptied (reference clipseg/segmentation.py:256-260).  The test pass fills it with three PNG files per image
+    (src/utils/viz.py) unless --no-viz; backup_test_run moves it."""
     import shutil
     viz_path = args.test_snapshot_path + "/viz"
     if os.path.exists(viz_path):
         shutil.rmtree(viz_path)
     os.makedirs(viz_path)
     return viz_path
+
+
+def visualize_seg(images, labels, preds, file_names, viz_path):
+    """The reference's visualize_seg (tools.py:278-315) for one batch in hand: per file name `<stem>.png` (ground truth red, prediction green),
+    `<stem>_overlay.png` (the same over channel 0 of the image) and `<stem>_pred.png` (the binary mask) under viz_path.  Device tensors: images
+    [B, 1|3, S, S] in [0, 1], labels [B, 1, S, S], preds the two-class logits [B, 2, S, S] or an arg-max mask [B, 1, S, S] / [B, S, S].  The pixels come
+    from one uia_seg_viz launch; returns once the files are written."""
+    import torch
+    from src.utils.viz import SegVisualizer
+    if preds.dim() == 3:
+        preds = preds[:, None]
+    if preds.shape[1] == 1:                                      # already a mask: class 1 wins where it is set
+        preds = torch.cat([torch.zeros_like(preds, dtype=torch.float32), (preds != 0).float()], dim=1)
+    os.makedirs(viz_path, exist_ok=True)
+    viz = SegVisualizer(viz_path, max_batch=len(file_names), size=preds.shape[-1], device=preds.device)
+    try:
+        viz.submit(images, labels, preds, file_names)
+    finally:
+        viz.close()

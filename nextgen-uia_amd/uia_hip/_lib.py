@@ -155,6 +155,8 @@ PROTOTYPES = {
     "uia_binary_cls_stats": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, sz, vp]),
     "uia_surface_distances_workspace_bytes": (sz, [C.c_int, C.c_int, C.c_int]),
     "uia_surface_distances": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, vp, f32, vp, sz, vp, vp]),
+    "uia_seg_viz_form": (C.c_int, [C.c_int, C.c_int, vp, vp, vp, vp, vp, vp]),
+    "uia_seg_viz": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int, vp, vp, vp]),
     "uia_retrieval_workspace_bytes": (sz, [C.c_int, C.c_int]),
     "uia_retrieval_ranks": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, C.c_int, vp, sz, vp, vp, vp, vp]),
     "uia_retrieval_stats_workspace_bytes": (sz, [C.c_int]),

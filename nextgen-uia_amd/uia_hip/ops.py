@@ -1797,6 +1797,43 @@ def surface_distances(logits, label, percentile=95.0):
     return hd, asd
 
 
+_SEG_LABEL = {torch.uint8: 0, torch.float32: 1}
+
+
+def _seg_viz_args(logits, images, labels, mask_rgb, overlay_rgb, pred):
+    _p(logits), _p(images), _p(labels)                            # CPU tensors are refused before anything else
+    _require(logits.dim() == 4 and logits.shape[2] == logits.shape[3], f"seg_viz: logits must be [B, C, S, S], got {tuple(logits.shape)}")
+    B, Cc, S, _ = logits.shape
+    _dense(logits, "seg_viz: logits", _F32)
+    _dense(images, "seg_viz: images", _F32)
+    _require(images.dim() == 4 and images.shape[0] == B and tuple(images.shape[2:]) == (S, S),
+             f"seg_viz: images {tuple(images.shape)} do not match logits {tuple(logits.shape)}")
+    _dense(labels, "seg_viz: labels", tuple(_SEG_LABEL), numel=B * S * S)
+    for t, name, n in ((mask_rgb, "mask_rgb", 3), (overlay_rgb, "overlay_rgb", 3), (pred, "pred", 1)):
+        _dense(t, f"seg_viz: {name}", (torch.uint8,), numel=B * S * S * n)
+        _require(t.device == logits.device, f"seg_viz: {name} is on {t.device}, logits on {logits.device}")
+    return B, Cc, images.shape[1], S, _SEG_LABEL[labels.dtype]
+
+
+def seg_viz_form(logits, images, labels, mask_rgb, overlay_rgb, pred):
+    """1 when seg_viz of these tensors runs on the four-pixels-per-thread kernel, 0 for the pixel-per-thread one (uia_seg_viz_form: size and addresses only)."""
+    _, _, _, S, code = _seg_viz_args(logits, images, labels, mask_rgb, overlay_rgb, pred)
+    return int(lib().uia_seg_viz_form(S, code, _p(logits), _p(images), _p(labels), _p(mask_rgb), _p(overlay_rgb), _p(pred)))
+
+
+def seg_viz(logits, images, labels, mask_rgb=None, overlay_rgb=None, pred=None):
+    """logits fp32 [B,2,S,S], images fp32 [B,1|3,S,S] (channel 0 is drawn), labels uint8 or fp32 [B,1,S,S], all contiguous -> (mask_rgb [B,S,S,3],
+    overlay_rgb [B,S,S,3], pred [B,S,S]), uint8: ground truth red and prediction green, the same over the grey input, and the binary mask, with the
+    arg-max rule of the Dice / IoU / surface metrics.  The outputs may be passed in (contiguous uint8 of those sizes).  Enqueued only: nothing is read back."""
+    if mask_rgb is None:
+        B, _, S, _ = logits.shape
+        mask_rgb, overlay_rgb = (torch.empty(B, S, S, 3, device=logits.device, dtype=torch.uint8) for _ in range(2))
+        pred = torch.empty(B, S, S, device=logits.device, dtype=torch.uint8)
+    B, Cc, Ci, S, code = _seg_viz_args(logits, images, labels, mask_rgb, overlay_rgb, pred)
+    check(lib().uia_seg_viz(_stream(), B, Cc, Ci, S, _p(logits), _p(images), _p(labels), code, _p(mask_rgb), _p(overlay_rgb), _p(pred)), "uia_seg_viz")
+    return mask_rgb, overlay_rgb, pred
+
+
 def retrieval_ranks(img, txt, normalize=True):
     """img, txt [N, E] paired features (non-fp32 is converted) -> (gt_i2t, eq_i2t, gt_t2i, eq_t2i), int32 device tensors [N]: for each query the number of
     OTHER candidates scoring strictly above / exactly equal to its own pair, s_ij = <img_i, txt_j> on the exact fp32 MFMA (rows L2-normalised first when
