@@ -565,6 +565,17 @@ size_t uia_augment_workspace_bytes(int B, int S);
 int uia_augment_batch(void* stream, int B, int S, const float* images, const uint8_t* masks, const int32_t* programs, void* ws, size_t ws_bytes,
                       float* out_images, uint8_t* out_masks);
 
+/* The same launch on a device-resident set (the few-shot entries' training set, uploaded once): output b is made from row `src` of images [N,1,S,S],
+ * where row 0 of output b in the table is (n, with_mask, src, 0) — the table format and its one host-to-device copy are those above.  src_dtype 0: the
+ * resident images are fp32 and the result is uia_augment_batch's on the gathered rows.  src_dtype 1: they are uint8, the 8-bit plane itself (no
+ * quantisation pass; an n == 0 row is written as (float)u / 255.0f): bit for bit uia_augment_batch on rows.float() / 255.  masks uint8 [N,1,S,S] or NULL.
+ * A row may serve any number of outputs and B may exceed N.  Checked before anything is enqueued, beside everything uia_augment_batch checks: N >= 1,
+ * src_dtype in {0, 1}, 0 <= src < N for every output, and the outputs ([B] rows) may not overlap the resident tensors ([N] rows).  Byte rows on 16 bytes
+ * move 16 bytes per access, rows on 4 bytes a word, others single bytes.  ws: uia_augment_workspace_bytes(B, S) — sized by B, not N.  Asynchronous,
+ * deterministic. */
+int uia_augment_gather(void* stream, int N, int B, int S, int src_dtype, const void* images, const uint8_t* masks, const int32_t* programs, void* ws,
+                       size_t ws_bytes, float* out_images, uint8_t* out_masks);
+
 /* ---------------------------------------------------------------------------------------------
  * Layout helpers around the GEMMs. */
 int uia_cast(void* stream, int dtype, size_t n, const float* src, void* dst, float scale);          /* dst = T(scale*src) */

@@ -1,5 +1,6 @@
 // augment.hip — the training-time augmentation of the reference's dataset modules (src/datasets/segmentation.py:14-156, classification.py:14-151) on the
-// device, one launch per batch: uia_augment_batch.
+// device, one launch per batch: uia_augment_batch, and its gathering form uia_augment_gather (the few-shot entries' resident training set: output b is
+// made from row `src` of an N-row resident tensor, fp32 or uint8; see the end of this comment).
 //
 // Every random decision is made on the host (src/datasets/augment.py) and arrives as a program table, int32 [B][14][4]: row 0 of an image is
 // (n, with_mask, 0, 0), rows 1 .. n (n <= 13) are (opcode, p0, p1, p2), float parameters as float32 bit patterns.  An image with n == 0 is copied bit for
@@ -30,6 +31,13 @@
 // separates the ops; a block's global writes are visible to its own later reads behind it.  Byte planes are 16-byte aligned and padded: point ops move 16
 // bytes per access; the fp32 input and output use 16-byte accesses where the image's first element is aligned (an operand one element into its buffer
 // takes the scalar path).  Integer atomics only.
+//
+// uia_augment_gather: row 0 of output b is (n, with_mask, src, 0) and block b reads resident row src (any row any number of times, B may exceed N) instead
+// of row b; everything behind the read is the code above, so an fp32 source gives what uia_augment_batch gives on the gathered rows.  A uint8 source IS
+// the 8-bit plane — rint(255 (u / 255)) = u for every byte in fp32 — so the quantisation pass becomes a byte copy into the first plane and an n == 0 row is
+// written as (float)u / 255.0f: both are, bit for bit, uia_augment_batch on rows.float() / 255.  Byte rows start at multiples of S^2 bytes: a row on 16
+// bytes moves 16 bytes per access, one on 4 bytes (S = 10) a word, any other (odd S) single bytes; the fp32 output keeps its 16-byte stores where
+// its own row is aligned.  The row index is checked on the host (0 <= src < N) and clamped again in the kernel.
 #include "uia_common.h"
 #include "uia_kernels.h"
 
@@ -179,7 +187,14 @@ __device__ void plane_histogram(const uint8_t* plane, int n, unsigned (*hist)[25
     __syncthreads();
 }
 
-__global__ __launch_bounds__(AUG_THREADS) void augment_kernel(int S, const float* __restrict__ images, const uint8_t* __restrict__ masks,
+__device__ __forceinline__ f32x4 bytes_to_unit(unsigned w) {
+    const f32x4 v = {(float)(w & 255u) / 255.0f, (float)((w >> 8) & 255u) / 255.0f, (float)((w >> 16) & 255u) / 255.0f, (float)(w >> 24) / 255.0f};
+    return v;
+}
+
+// GATHER: block b reads resident row prog[2] of `rows` (else row b).  BYTES: the source is the 8-bit plane itself (else fp32 in [0, 1]).
+template <bool GATHER, bool BYTES>
+__global__ __launch_bounds__(AUG_THREADS) void augment_kernel(int S, int rows, const void* __restrict__ images, const uint8_t* __restrict__ masks,
                                                               const int32_t* __restrict__ table, uint8_t* __restrict__ planes, uint8_t* __restrict__ mplanes,
                                                               float* __restrict__ fplanes, size_t P, float* __restrict__ out_images,
                                                               uint8_t* __restrict__ out_masks) {
@@ -196,16 +211,39 @@ __global__ __launch_bounds__(AUG_THREADS) void augment_kernel(int S, const float
     const int N = S * S;
     const int32_t* prog = table + b * AUG_ROWS * 4;
     const int n_ops = min(max(prog[0], 0), AUG_MAX_OPS);
-    const float* src = images + b * (size_t)N;
+    const size_t row = GATHER ? (size_t)min(max(prog[2], 0), rows - 1) : b;
+    const float* src = (const float*)images + row * (size_t)N;                     // the fp32 source ...
+    const uint8_t* usrc = (const uint8_t*)images + row * (size_t)N;               // ... or the byte source
     float* dst = out_images + b * (size_t)N;
-    const uint8_t* msrc = masks ? masks + b * (size_t)N : nullptr;
+    const uint8_t* msrc = masks ? masks + row * (size_t)N : nullptr;
     uint8_t* mdst = masks ? out_masks + b * (size_t)N : nullptr;
-    const bool vec = (((uintptr_t)src | (uintptr_t)dst) & 15) == 0;
+    const bool vec = ((BYTES ? (uintptr_t)dst : ((uintptr_t)src | (uintptr_t)dst)) & 15) == 0;
     const int quads = vec ? N >> 2 : 0;                        // elements 4·quads .. N - 1 go one by one
+    const int ualign = !BYTES ? 0 : (((uintptr_t)usrc & 15) == 0 ? 16 : (((uintptr_t)usrc & 3) == 0 ? 4 : 1));
 
     if (n_ops == 0) {                                           // bit for bit
-        for (int q = tid; q < quads; q += AUG_THREADS) *(f32x4*)(dst + 4 * (size_t)q) = *(const f32x4*)(src + 4 * (size_t)q);
-        for (int i = 4 * quads + tid; i < N; i += AUG_THREADS) dst[i] = src[i];
+        if (BYTES) {                                            // ... of rows.float() / 255
+            int done = 0;
+            if (vec && ualign == 16) {
+                const int chunks = N >> 4;
+                for (int c = tid; c < chunks; c += AUG_THREADS) {
+                    const uint4 v = *(const uint4*)(usrc + 16 * (size_t)c);
+                    float* d = dst + 16 * (size_t)c;
+                    *(f32x4*)d = bytes_to_unit(v.x);
+                    *(f32x4*)(d + 4) = bytes_to_unit(v.y);
+                    *(f32x4*)(d + 8) = bytes_to_unit(v.z);
+                    *(f32x4*)(d + 12) = bytes_to_unit(v.w);
+                }
+                done = 16 * chunks;
+            } else if (vec && ualign == 4) {
+                for (int q = tid; q < quads; q += AUG_THREADS) *(f32x4*)(dst + 4 * (size_t)q) = bytes_to_unit(*(const unsigned*)(usrc + 4 * (size_t)q));
+                done = 4 * quads;
+            }
+            for (int i = done + tid; i < N; i += AUG_THREADS) dst[i] = (float)usrc[i] / 255.0f;
+        } else {
+            for (int q = tid; q < quads; q += AUG_THREADS) *(f32x4*)(dst + 4 * (size_t)q) = *(const f32x4*)(src + 4 * (size_t)q);
+            for (int i = 4 * quads + tid; i < N; i += AUG_THREADS) dst[i] = src[i];
+        }
         if (msrc)
             for_pixels(mdst, N, [&](int i) { return msrc[i]; });
         return;
@@ -218,12 +256,26 @@ __global__ __launch_bounds__(AUG_THREADS) void augment_kernel(int S, const float
     int mslot = 0;                                              // the mask plane the next geometry op writes
     float* fp = fplanes + b * P;
 
-    auto quant = [](float x) { return (uint8_t)(int)fminf(fmaxf(rintf(x * 255.0f), 0.f), 255.f); };      // fmaxf(NaN, 0) = 0
-    for (int q = tid; q < quads; q += AUG_THREADS) {
-        const f32x4 v = *(const f32x4*)(src + 4 * (size_t)q);
-        *(unsigned*)(cur + 4 * (size_t)q) = (unsigned)quant(v[0]) | ((unsigned)quant(v[1]) << 8) | ((unsigned)quant(v[2]) << 16) | ((unsigned)quant(v[3]) << 24);
+    if (BYTES) {                                                // the source is the plane: copied, never rounded (cur is 16-byte aligned)
+        int done = 0;
+        if (ualign == 16) {
+            const int chunks = N >> 4;
+            for (int c = tid; c < chunks; c += AUG_THREADS) *(uint4*)(cur + 16 * (size_t)c) = *(const uint4*)(usrc + 16 * (size_t)c);
+            done = 16 * chunks;
+        } else if (ualign == 4) {
+            const int words = N >> 2;
+            for (int q = tid; q < words; q += AUG_THREADS) *(unsigned*)(cur + 4 * (size_t)q) = *(const unsigned*)(usrc + 4 * (size_t)q);
+            done = 4 * words;
+        }
+        for (int i = done + tid; i < N; i += AUG_THREADS) cur[i] = usrc[i];
+    } else {
+        auto quant = [](float x) { return (uint8_t)(int)fminf(fmaxf(rintf(x * 255.0f), 0.f), 255.f); };      // fmaxf(NaN, 0) = 0
+        for (int q = tid; q < quads; q += AUG_THREADS) {
+            const f32x4 v = *(const f32x4*)(src + 4 * (size_t)q);
+            *(unsigned*)(cur + 4 * (size_t)q) = (unsigned)quant(v[0]) | ((unsigned)quant(v[1]) << 8) | ((unsigned)quant(v[2]) << 16) | ((unsigned)quant(v[3]) << 24);
+        }
+        for (int i = 4 * quads + tid; i < N; i += AUG_THREADS) cur[i] = quant(src[i]);
     }
-    for (int i = 4 * quads + tid; i < N; i += AUG_THREADS) cur[i] = quant(src[i]);
     __syncthreads();
 
     for (int o = 0; o < n_ops; ++o) {
@@ -428,9 +480,7 @@ __global__ __launch_bounds__(AUG_THREADS) void augment_kernel(int S, const float
     }
 
     for (int q = tid; q < quads; q += AUG_THREADS) {
-        const unsigned w = *(const unsigned*)(cur + 4 * (size_t)q);
-        const f32x4 v = {(float)(w & 255u) / 255.0f, (float)((w >> 8) & 255u) / 255.0f, (float)((w >> 16) & 255u) / 255.0f, (float)(w >> 24) / 255.0f};
-        *(f32x4*)(dst + 4 * (size_t)q) = v;
+        *(f32x4*)(dst + 4 * (size_t)q) = bytes_to_unit(*(const unsigned*)(cur + 4 * (size_t)q));
     }
     for (int i = 4 * quads + tid; i < N; i += AUG_THREADS) dst[i] = (float)cur[i] / 255.0f;
     if (mcur)
@@ -444,43 +494,77 @@ size_t uia_augment_ws_bytes(int B, int S) {
     return aug_layout(B, S).total;
 }
 
-int uia_augment_batch_launch(hipStream_t stream, int B, int S, const float* images, const uint8_t* masks, const int32_t* programs, void* ws, size_t ws_bytes,
-                             float* out_images, uint8_t* out_masks) {
-    UIA_CHECK_ARG(B >= 1 && B <= AUG_MAX_B && S >= AUG_MIN_S && S <= AUG_MAX_S, "uia_augment_batch: bad shape B=%d S=%d (1 <= B <= %d, %d <= S <= %d)", B, S,
-                  AUG_MAX_B, AUG_MIN_S, AUG_MAX_S);
-    UIA_CHECK_ARG(images && programs && ws && out_images, "uia_augment_batch: null tensor");
-    UIA_CHECK_ARG((masks == nullptr) == (out_masks == nullptr), "uia_augment_batch: masks and out_masks go together");
-    const size_t npix = (size_t)B * S * S;                          // block b reads image b and writes output b: any overlap of the two ranges is a race
-    auto overlap = [](const void* a, const void* b, size_t bytes) {
-        return (uintptr_t)a < (uintptr_t)b + bytes && (uintptr_t)b < (uintptr_t)a + bytes;
+namespace {
+
+// Every check of both entry points, before anything is enqueued.  rows == 0: uia_augment_batch (image b is row b of B, fp32); rows >= 1: uia_augment_gather.
+int aug_check(const char* who, int rows, int B, int S, int src_dtype, const void* images, const uint8_t* masks, const int32_t* programs, void* ws,
+              size_t ws_bytes, float* out_images, uint8_t* out_masks) {
+    const bool gather = rows != 0;
+    UIA_CHECK_ARG(B >= 1 && B <= AUG_MAX_B && S >= AUG_MIN_S && S <= AUG_MAX_S, "%s: bad shape B=%d S=%d (1 <= B <= %d, %d <= S <= %d)", who, B, S, AUG_MAX_B,
+                  AUG_MIN_S, AUG_MAX_S);
+    if (gather) {
+        UIA_CHECK_ARG(rows >= 1, "%s: a resident set of N=%d rows (N >= 1)", who, rows);
+        UIA_CHECK_ARG(src_dtype == 0 || src_dtype == 1, "%s: src_dtype %d (0 fp32, 1 uint8)", who, src_dtype);
+    }
+    UIA_CHECK_ARG(images && programs && ws && out_images, "%s: null tensor", who);
+    UIA_CHECK_ARG((masks == nullptr) == (out_masks == nullptr), "%s: masks and out_masks go together", who);
+    const size_t pix = (size_t)S * S, in_rows = gather ? (size_t)rows : (size_t)B, elt = src_dtype == 1 ? 1 : sizeof(float);
+    auto overlap = [](const void* a, size_t na, const void* b, size_t nb) {        // a block reads its source row and writes output b: any overlap is a race
+        return (uintptr_t)a < (uintptr_t)b + nb && (uintptr_t)b < (uintptr_t)a + na;
     };
-    UIA_CHECK_ARG(!overlap(images, out_images, npix * sizeof(float)) && (!masks || !overlap(masks, out_masks, npix)),
-                  "uia_augment_batch: the outputs must not be the inputs (the ranges overlap)");
-    UIA_CHECK_ARG((uintptr_t)ws % 16 == 0 && (uintptr_t)images % 4 == 0 && (uintptr_t)out_images % 4 == 0,
-                  "uia_augment_batch: the workspace must be 16-byte aligned, the images 4-byte aligned");
+    UIA_CHECK_ARG(!overlap(images, in_rows * pix * elt, out_images, (size_t)B * pix * sizeof(float)) &&
+                      (!masks || !overlap(masks, in_rows * pix, out_masks, (size_t)B * pix)),
+                  "%s: the outputs must not be the inputs (the ranges overlap)", who);
+    UIA_CHECK_ARG((uintptr_t)ws % 16 == 0 && (uintptr_t)images % elt == 0 && (uintptr_t)out_images % 4 == 0,
+                  "%s: the workspace must be 16-byte aligned, the images 4-byte aligned", who);
     const AugLayout l = aug_layout(B, S);
-    UIA_CHECK_ARG(ws_bytes >= l.total, "uia_augment_batch: workspace of %zu bytes, %zu needed", ws_bytes, l.total);
+    UIA_CHECK_ARG(ws_bytes >= l.total, "%s: workspace of %zu bytes, %zu needed", who, ws_bytes, l.total);
     for (int b = 0; b < B; ++b) {                                  // the whole table is checked before anything is enqueued
         const int32_t* p = programs + (size_t)b * AUG_ROWS * 4;
-        UIA_CHECK_ARG(p[0] >= 0 && p[0] <= AUG_MAX_OPS, "uia_augment_batch: image %d has %d ops (0 .. %d)", b, p[0], AUG_MAX_OPS);
+        UIA_CHECK_ARG(p[0] >= 0 && p[0] <= AUG_MAX_OPS, "%s: image %d has %d ops (0 .. %d)", who, b, p[0], AUG_MAX_OPS);
+        if (gather) UIA_CHECK_ARG(p[2] >= 0 && p[2] < rows, "%s: output %d is made from row %d of a resident set of %d rows", who, b, p[2], rows);
         for (int o = 1; o <= p[0]; ++o) {
             const int code = p[4 * o], p0 = p[4 * o + 1], p1 = p[4 * o + 2], p2 = p[4 * o + 3];
             const float pf = __builtin_bit_cast(float, p0);
-            UIA_CHECK_ARG(code >= 0 && code < OP_COUNT, "uia_augment_batch: image %d op %d: unknown opcode %d", b, o - 1, code);
-            if (code == OP_BLUR) UIA_CHECK_ARG(pf >= 0.1f && pf <= 2.5f, "uia_augment_batch: image %d op %d: blur sigma %g outside [0.1, 2.5]", b, o - 1, (double)pf);
+            UIA_CHECK_ARG(code >= 0 && code < OP_COUNT, "%s: image %d op %d: unknown opcode %d", who, b, o - 1, code);
+            if (code == OP_BLUR) UIA_CHECK_ARG(pf >= 0.1f && pf <= 2.5f, "%s: image %d op %d: blur sigma %g outside [0.1, 2.5]", who, b, o - 1, (double)pf);
             if (code == OP_CONTRAST || code == OP_BRIGHTNESS || code == OP_SHARPNESS)
-                UIA_CHECK_ARG(pf >= 0.f && pf <= 4.f, "uia_augment_batch: image %d op %d: factor %g outside [0, 4]", b, o - 1, (double)pf);
-            if (code == OP_POSTERIZE) UIA_CHECK_ARG(p0 >= 1 && p0 <= 8, "uia_augment_batch: image %d op %d: posterize to %d bits (1 .. 8)", b, o - 1, p0);
-            if (code == OP_SOLARIZE) UIA_CHECK_ARG(p0 >= 0 && p0 <= 256, "uia_augment_batch: image %d op %d: solarize threshold %d (0 .. 256)", b, o - 1, p0);
+                UIA_CHECK_ARG(pf >= 0.f && pf <= 4.f, "%s: image %d op %d: factor %g outside [0, 4]", who, b, o - 1, (double)pf);
+            if (code == OP_POSTERIZE) UIA_CHECK_ARG(p0 >= 1 && p0 <= 8, "%s: image %d op %d: posterize to %d bits (1 .. 8)", who, b, o - 1, p0);
+            if (code == OP_SOLARIZE) UIA_CHECK_ARG(p0 >= 0 && p0 <= 256, "%s: image %d op %d: solarize threshold %d (0 .. 256)", who, b, o - 1, p0);
             if (code == OP_CROP)
                 UIA_CHECK_ARG(p0 >= 0 && p1 >= 0 && p2 >= 1 && p2 <= S && p0 <= S - p2 && p1 <= S - p2,
-                              "uia_augment_batch: image %d op %d: crop (i=%d, j=%d, side=%d) leaves the %d x %d image", b, o - 1, p0, p1, p2, S, S);
+                              "%s: image %d op %d: crop (i=%d, j=%d, side=%d) leaves the %d x %d image", who, b, o - 1, p0, p1, p2, S, S);
         }
     }
+    return 0;
+}
+
+template <bool GATHER, bool BYTES>
+int aug_launch(hipStream_t stream, int rows, int B, int S, const void* images, const uint8_t* masks, const int32_t* programs, void* ws, float* out_images,
+               uint8_t* out_masks) {
+    const AugLayout l = aug_layout(B, S);
     char* base = (char*)ws;
     UIA_CHECK_HIP(hipMemcpyAsync(base + l.table, programs, (size_t)B * AUG_ROWS * 4 * sizeof(int32_t), hipMemcpyHostToDevice, stream));
-    hipLaunchKernelGGL(augment_kernel, dim3((unsigned)B), dim3(AUG_THREADS), 0, stream, S, images, masks, (const int32_t*)(base + l.table),
-                       (uint8_t*)(base + l.planes), (uint8_t*)(base + l.mplanes), (float*)(base + l.fplane), l.P, out_images, out_masks);
+    augment_kernel<GATHER, BYTES><<<dim3((unsigned)B), dim3(AUG_THREADS), 0, stream>>>(S, rows, images, masks, (const int32_t*)(base + l.table),
+                                                                                      (uint8_t*)(base + l.planes), (uint8_t*)(base + l.mplanes),
+                                                                                      (float*)(base + l.fplane), l.P, out_images, out_masks);
     UIA_CHECK_LAUNCH();
     return 0;
+}
+
+}  // namespace
+
+int uia_augment_batch_launch(hipStream_t stream, int B, int S, const float* images, const uint8_t* masks, const int32_t* programs, void* ws, size_t ws_bytes,
+                             float* out_images, uint8_t* out_masks) {
+    if (int rc = aug_check("uia_augment_batch", 0, B, S, 0, images, masks, programs, ws, ws_bytes, out_images, out_masks)) return rc;
+    return aug_launch<false, false>(stream, B, B, S, images, masks, programs, ws, out_images, out_masks);
+}
+
+int uia_augment_gather_launch(hipStream_t stream, int N, int B, int S, int src_dtype, const void* images, const uint8_t* masks, const int32_t* programs,
+                              void* ws, size_t ws_bytes, float* out_images, uint8_t* out_masks) {
+    UIA_CHECK_ARG(N >= 1, "uia_augment_gather: a resident set of N=%d rows (N >= 1)", N);
+    if (int rc = aug_check("uia_augment_gather", N, B, S, src_dtype, images, masks, programs, ws, ws_bytes, out_images, out_masks)) return rc;
+    return src_dtype == 1 ? aug_launch<true, true>(stream, N, B, S, images, masks, programs, ws, out_images, out_masks)
+                          : aug_launch<true, false>(stream, N, B, S, images, masks, programs, ws, out_images, out_masks);
 }

@@ -277,6 +277,10 @@ int uia_augment_batch(void* stream, int B, int S, const float* images, const uin
                       float* out_images, uint8_t* out_masks) {
     return uia_augment_batch_launch((hipStream_t)stream, B, S, images, masks, programs, ws, ws_bytes, out_images, out_masks);
 }
+int uia_augment_gather(void* stream, int N, int B, int S, int src_dtype, const void* images, const uint8_t* masks, const int32_t* programs, void* ws,
+                       size_t ws_bytes, float* out_images, uint8_t* out_masks) {
+    return uia_augment_gather_launch((hipStream_t)stream, N, B, S, src_dtype, images, masks, programs, ws, ws_bytes, out_images, out_masks);
+}
 
 int uia_im2col_padded(void* stream, int dtype, int B, int C, int H, int W, int P, const float* img, void* cols, int64_t ldo) {
     return uia_im2col_padded_launch((hipStream_t)stream, dtype, B, C, H, W, P, img, cols, (long)ldo);

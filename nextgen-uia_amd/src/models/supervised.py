@@ -1,5 +1,7 @@
 """The supervised training loop of the classification and segmentation entry points: `train`, `test`, `run` (the body of every `main`), the build's
-shared flags (`add_build_args`) and the two task descriptions the loop reads (`CLASSIFICATION`, `SEGMENTATION`).
+shared flags (`add_build_args`) and the task descriptions the loop reads (`CLASSIFICATION`, `SEGMENTATION`, and their few-shot forms
+`FEWSHOT_CLASSIFICATION`, `FEWSHOT_SEGMENTATION`: the reference's src/models/{biomedclip,baselines}/fewshot_*.py — the same loops on a training list
+sampled once (src/datasets/fewshot_*.py), whose batches are formed on the device from the resident set (src/datasets/resident.py); one process).
 
 What the reference repeats per family (src/models/*/classification.py, src/models/*/segmentation.py): FocalLoss / DiceCE per iteration, AdamW with a
 per-iteration cosine schedule and no clipping, validation at `epoch > 0 and epoch % 10 == 0` and at the last epoch, the best checkpoint by a strict >
@@ -16,6 +18,7 @@ dict of extra forward keyword arguments)`, called once behind the model's prepar
 `checkpoint_dict()` and `load_checkpoint(state)`.
 """
 import argparse
+import dataclasses
 import functools
 import logging
 import os
@@ -27,8 +30,11 @@ import numpy as np
 import torch
 
 from src.datasets import classification as dataset_cls
+from src.datasets import fewshot_classification as dataset_fs_cls
+from src.datasets import fewshot_segmentation as dataset_fs_seg
 from src.datasets import segmentation as dataset_seg
 from src.datasets.augment import stage_for
+from src.datasets.resident import resident_for
 from src.losses.dice import DiceCELoss
 from src.losses.focal import FocalLoss
 from src.utils.cls_metrics import ClassificationMetrics, report_cls_test
@@ -58,6 +64,10 @@ class Task:
     loop_timings: bool = False      # epoch records carry loader_wait_ms / enqueue_ms / drain_ms
     stop_twice: bool = False        # the reference's second early-stopping line
     visualize: bool = False         # test() writes the reference's three pictures per test image into <test dir>/viz (src/utils/viz.py) unless --no-viz
+    train_module: object = None     # (args, rank=, world=) -> the data module of train(); None: data.DataModule.  test() always uses data.DataModule
+    resident: bool = False          # training batches are formed on the device from the module's resident_rows() (src/datasets/resident.py): no training
+                                    # loader; the module carries original_train_count / sampled_train_count, which train()'s dict repeats
+    roc_csv: bool = False           # after each validation: <train dir>/roc_curves/roc_curve_iter_<iter>.csv (the data of the reference's plot_roc_curve)
 
 
 def _cls_input(images, labels, in_channels, bufs=None):
@@ -82,6 +92,8 @@ CLASSIFICATION = Task(data=dataset_cls, criterion=FocalLoss(to_onehot_y=True), m
 SEGMENTATION = Task(data=dataset_seg, criterion=DiceCELoss(smooth_nr=1e-8, smooth_dr=1e-8), metrics=_seg_metrics, report=report_test, best="dice_mean", best_name="best_val_dice", best_words="a mean Dice", scalars=("loss", "dice_mean", "iou_mean"),
                     line=_seg_line, to_input=functools.partial(dataset_seg.as_model_input, widen=False), with_mask=True, data_parallel=True,
                     val_history=False, visualize=True)
+FEWSHOT_CLASSIFICATION = dataclasses.replace(CLASSIFICATION, train_module=dataset_fs_cls.from_args, resident=True, roc_csv=True)
+FEWSHOT_SEGMENTATION = dataclasses.replace(SEGMENTATION, train_module=dataset_fs_seg.from_args, resident=True, data_parallel=False)
 
 
 def add_build_args(p, synthetic_train=256):
@@ -137,9 +149,19 @@ def evaluate(task, model, loader_pf, accumulator, in_channels=3, kwargs_for=_no_
                 seen += images.shape[0]
 
 
-def _split_pass(task, model, loader_pf, accumulator, args, kwargs_for, writer, split, iter_num):
+def _write_roc_csv(accumulator, folder, iter_num):
+    fpr, tpr, thr = (t.cpu().tolist() for t in accumulator.roc())
+    os.makedirs(folder, exist_ok=True)
+    with open(os.path.join(folder, f"roc_curve_iter_{iter_num}.csv"), "w") as f:
+        f.write("fpr,tpr,threshold\n")
+        f.writelines(f"{a!r},{b!r},{c!r}\n" for a, b, c in zip(fpr, tpr, thr))
+
+
+def _split_pass(task, model, loader_pf, accumulator, args, kwargs_for, writer, split, iter_num, roc_dir=None):
     evaluate(task, model, loader_pf, accumulator, args.in_channels, kwargs_for)
     stats = accumulator.compute()
+    if roc_dir is not None:
+        _write_roc_csv(accumulator, roc_dir, iter_num)
     accumulator.reset()
     for k in task.scalars:
         writer.add_scalar(f"{args.exp}/{split}_{k.replace('_mean', '')}", stats[k], iter_num)
@@ -148,11 +170,14 @@ def _split_pass(task, model, loader_pf, accumulator, args, kwargs_for, writer, s
 
 
 def train(args, task, prepare, forward_kwargs=None):
-    rank, _, world = dist_env() if task.data_parallel else (0, 0, 1)
+    rank, _, world = dist_env() if task.data_parallel or task.resident else (0, 0, 1)      # resident: the module refuses a world above 1
     if not torch.cuda.is_initialized():
         torch.set_num_threads(max(1, min(4, torch.get_num_threads())))
-    dm = task.data.DataModule(args, rank=rank, world=world)
-    trainloader, valloader, testloader = dm.train_dataloader(), dm.val_dataloader(), dm.test_dataloader()
+    dm = (task.train_module or task.data.DataModule)(args, rank=rank, world=world)
+    if task.resident:
+        logging.info(f"Training samples: {dm.sampled_train_count} / {dm.original_train_count}")
+    trainloader = None if task.resident else dm.train_dataloader()
+    valloader, testloader = dm.val_dataloader(), dm.test_dataloader()
     dm.start_workers()                                           # loader worker processes are forked BEFORE this process touches the GPU
     _bind(args, task)
     UF.set_dropout_seed(args.seed + 7919 * rank)
@@ -166,15 +191,17 @@ def train(args, task, prepare, forward_kwargs=None):
                                weight_decay=args.weight_decay, max_norm=0.0)              # no clipping in these loops
     if world > 1:
         init_data_parallel(opt)
-    max_iters = len(trainloader) * args.epochs
     second = task.data.second_of
-    train_pf, val_pf, test_pf = (DevicePrefetcher(loader, None, args.device, second=second) for loader in (trainloader, valloader, testloader))
+    train_pf = resident_for(args, dm, rank) if task.resident else DevicePrefetcher(trainloader, None, args.device, second=second)
+    val_pf, test_pf = (DevicePrefetcher(loader, None, args.device, second=second) for loader in (valloader, testloader))
+    max_iters = len(train_pf if task.resident else trainloader) * args.epochs
     best_path = os.path.join(args.train_snapshot_path, "best_model.pth")
     iter_num, best, patience, logged, last = 0, 0.0, 0, [], None
     epoch_ms, val_hist = [], []
     cur = torch.cuda.current_stream()
     bufs = {}                                                    # a widened training batch lives in the same two tensors every iteration
-    augment = stage_for(args, with_mask=task.with_mask, rank=rank)         # --strong_augs / --weak_augs on --data_pt batches; None: bypassed
+    # --strong_augs / --weak_augs on --data_pt batches; None: bypassed, or (resident) run by the launch that forms the batch
+    augment = None if task.resident else stage_for(args, with_mask=task.with_mask, rank=rank)
     criterion, to_input, with_mask, ahead, in_channels = task.criterion, task.to_input, task.with_mask, task.data_parallel, args.in_channels
     lr_max, lr_min, clock = args.lr, args.lr_min, time.perf_counter
     batches = None
@@ -186,6 +213,8 @@ def train(args, task, prepare, forward_kwargs=None):
         t0, w0, enq, n_it = clock(), train_pf.wait_s, 0.0, 0
         if augment is not None:
             augment.set_epoch(epoch)
+        if task.resident:
+            train_pf.set_epoch(epoch)
         if not ahead:
             batches = iter(train_pf)
         for images, labels, ready in batches:
@@ -221,7 +250,8 @@ def train(args, task, prepare, forward_kwargs=None):
         last = float(logged[-1][1]) if logged else last
         logged = []
         accumulator = task.metrics(criterion=criterion, num_classes=args.num_classes)
-        stats = _split_pass(task, model, val_pf, accumulator, args, kwargs_for, writer, "val", iter_num)
+        roc_dir = os.path.join(args.train_snapshot_path, "roc_curves") if task.roc_csv and rank == 0 else None
+        stats = _split_pass(task, model, val_pf, accumulator, args, kwargs_for, writer, "val", iter_num, roc_dir)
         val_hist.append({"epoch": epoch, **stats})
         if stats[task.best] > best:
             patience, best = 0, stats[task.best]
@@ -252,6 +282,8 @@ def train(args, task, prepare, forward_kwargs=None):
                         "and fails in test())")
         torch.save(model.checkpoint_dict(), best_path)
     out = {"iters": iter_num, task.best_name: best, "last_loss": last, "epochs": epoch_ms, "augmented_images": augment.augmented if augment is not None else 0}
+    if task.resident:
+        out.update(augmented_images=train_pf.augmented, original_train_count=dm.original_train_count, sampled_train_count=dm.sampled_train_count)
     if task.data_parallel:
         out.update(rank=rank, world=world)
     if task.val_history:

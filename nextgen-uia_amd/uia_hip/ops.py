@@ -1922,6 +1922,38 @@ def augment_batch(images, masks, programs, out_images=None, out_masks=None, ws=N
     return out_images, out_masks
 
 
+def augment_gather(images, masks, programs, out_images=None, out_masks=None, ws=None):
+    """augment_batch on a device-resident set: images [N, 1, S, S], fp32 in [0, 1] or uint8 (the 8-bit plane as stored), masks uint8 [N, 1, S, S]
+    or None, programs a HOST int32 tensor [B, 14, 4] whose row 0 of output b is (n, with_mask, src, 0): output b is resident row src run through its
+    program (n == 0: the row itself; bytes as u / 255) -> (out_images fp32 [B, 1, S, S], out_masks uint8 [B, 1, S, S] or None).  One table copy and
+    one launch; equal, bit for bit, to augment_batch(images[src] (bytes: .float() / 255), programs).  Rows may repeat and B may exceed N."""
+    _p(images), _p(masks)
+    if (images.dim() != 4 or images.shape[1] != 1 or images.shape[2] != images.shape[3] or images.dtype not in (torch.float32, torch.uint8)
+            or not images.is_contiguous() or images.shape[0] < 1):
+        raise UiaError(f"augment_gather: images must be contiguous fp32 or uint8 [N, 1, S, S], got {images.dtype} {tuple(images.shape)}")
+    N, _, S, _ = images.shape
+    if masks is not None and (masks.shape != images.shape or masks.dtype != torch.uint8 or not masks.is_contiguous() or masks.device != images.device):
+        raise UiaError(f"augment_gather: masks must be contiguous uint8 {tuple(images.shape)} beside the images, got {masks.dtype} {tuple(masks.shape)}")
+    if (not isinstance(programs, torch.Tensor) or programs.is_cuda or programs.dtype != torch.int32 or programs.dim() != 3
+            or tuple(programs.shape[1:]) != (AUG_ROWS, 4) or programs.shape[0] < 1 or not programs.is_contiguous()):
+        raise UiaError(f"augment_gather: programs must be a contiguous host int32 tensor [B, {AUG_ROWS}, 4]")
+    B = programs.shape[0]
+    if out_images is None:
+        out_images = torch.empty((B, 1, S, S), dtype=torch.float32, device=images.device)
+    if masks is not None and out_masks is None:
+        out_masks = torch.empty((B, 1, S, S), dtype=torch.uint8, device=images.device)
+    if masks is None:
+        out_masks = None
+    for o, dt, name in ((out_images, torch.float32, "out_images"), (out_masks, torch.uint8, "out_masks")):
+        if o is not None and (tuple(o.shape) != (B, 1, S, S) or o.dtype != dt or not o.is_contiguous() or o.device != images.device):
+            raise UiaError(f"augment_gather: {name} must be contiguous {dt} [{B}, 1, {S}, {S}] on the images' device")
+    if ws is None:
+        ws = augment_workspace(B, S, images.device)
+    check(lib().uia_augment_gather(_stream(), N, B, S, 1 if images.dtype == torch.uint8 else 0, _p(images), _p(masks), programs.data_ptr(), _p(ws),
+                                   ws.numel(), _p(out_images), _p(out_masks)), "uia_augment_gather")
+    return out_images, out_masks
+
+
 # ---------------------------------------------------------------- DINOv2 UNet decoder (csrc/unet_conv.hip, unet_bn.hip, unet_resample.hip)
 CONV3, CONVT_FWD, CONVT_BWD, CONV1 = 0, 1, 2, 3      # uia_conv_igemm / uia_conv_wgrad modes
 BN_SLICES = 256                            # UIA_BN_SLICES
