@@ -8,32 +8,25 @@ early stopping, runs/<exp>/{log.log,best_model.pth}.  Added, non-breaking: --dty
 has no network), and data parallelism when launched under torch.distributed.run (one process per GPU, one RCCL
 all-reduce of the flat adapter-gradient buffer per optimiser update ≡ the reference's accumulation).
 
-What differs underneath: encode_image / encode_text / loss / backward / optimiser run in libuia_hip.so (uia_hip.*).
+What differs underneath: encode_image / encode_text / loss / backward / optimiser run in libuia_hip.so (uia_hip.*); the loop is
+src/models/contrastive.py with its BIOMEDCLIP recipe, this module keeps the flags and the model.
 `--method full` (the reference's default): the image tower trains through op-level functions with `uia_wgrad` weight gradients
 (all blocks or --tune_layers last3/6/9, lr forced to 1e-6 as in reference :153-155, whole state dict checkpointed); with
 --tune_text_encoder the BERT weights, LayerNorms and embedding tables train as well (`uia_embed_bwd`).
 """
 import argparse
 import logging
-import math
-import os
-import random
 import sys
-import time
 from pathlib import Path
 
 sys.path.insert(0, str(Path(__file__).resolve().parents[3]))
 
-import numpy as np
 import torch
 
 from src.adapters import inject_lora_to_biomedclip, inject_mona_variant_to_open_clip
-from src.datasets import finetune as dataset_finetune
-from src.losses import InfoNCELoss
+from src.models import contrastive
 from src.third_party.biomedclip.model import SyntheticTokenizer, create_biomedclip
-from src.utils.tools import default_device, model_summary, parse_config, setup_logging
-from uia_hip import functional as UF
-from uia_hip.engine import ContrastiveLoop, DevicePrefetcher, FlatAdapterOptimizer, bind_device, dist_env, init_data_parallel, sum_over_ranks
+from src.utils.tools import default_device, parse_config
 
 
 def get_args(argv=None):
@@ -69,13 +62,8 @@ def get_args(argv=None):
     p.add_argument("--accumulation_steps", type=int, default=4)
     p.add_argument("--grad_clip", type=float, default=1.0)
     # additions of this build
-    p.add_argument("--dtype", type=str, default="bf16", choices=["bf16", "fp32"], help="operand precision of the HIP kernels")
-    p.add_argument("--synthetic", action="store_true", help="synthetic image-caption pairs (no dataset files needed)")
-    p.add_argument("--synthetic_train", type=int, default=512)
-    p.add_argument("--synthetic_val", type=int, default=128)
-    p.add_argument("--data_pt", type=str, default=None, help=".pt with {'images': [N,3,S,S], 'texts': [str]}")
+    contrastive.add_build_args(p)
     p.add_argument("--ckpt_path", type=str, default=None, help="open_clip BiomedCLIP state dict (.pt); random init if absent")
-    p.add_argument("--model_config", type=str, default=None, help="python dict literal overriding the BiomedCLIP geometry (tests)")
     p.add_argument("--stats_json", type=str, default=None, help="write train()'s return value (per-epoch wall time and update counts included) to this file")
     return p.parse_args(argv)
 
@@ -136,118 +124,15 @@ def prepare_model(args):
     return model, tokenizer
 
 
-def _save_checkpoint(model, args, save_path):
-    if args.method == "full":                                    # reference :200-208: the whole state dict
-        torch.save(model.state_dict(), save_path)
-        return
-    key = "mona" if args.method == "mona" else "lora"
-    torch.save({n: p.data.clone() for n, p in model.named_parameters() if key in n.lower()}, save_path)
+RECIPE = contrastive.BIOMEDCLIP
 
 
 def train(args):
-    """The loop of reference :211-361 on the measured step: every loader batch goes through engine.ContrastiveLoop.micro (contrastive_micro: text tower on its
-    own stream, image tower in two slices, three-byte residual gradients; guarded accumulate) and every accumulation boundary through the device-guarded
-    clip + AdamW — the same functions bench.py times.  The host reads nothing per batch: the non-finite skip (:281-285) is decided on the device, the epoch's
-    loss sum / counts / skipped indices come back in ONE read at the end of the epoch, batches arrive through a double-buffered prefetcher."""
-    rank, _, world = dist_env()
-    if not torch.cuda.is_initialized():                         # a fresh CLI process (not a caller that is already running other GPU / CPU work in this process)
-        torch.set_num_threads(max(1, min(4, torch.get_num_threads())))      # host tensor work here is one staging copy per batch; the default (every logical CPU of the node) oversubscribes a job's CPU share
-    dm = dataset_finetune.DataModule(args, rank=rank, world=world, tokenizer=make_tokenizer(args))
-    trainloader, valloader = dm.train_dataloader(), dm.val_dataloader()
-    dm.start_workers()                                         # loader worker processes are forked BEFORE this process touches the GPU
-    bind_device(args)                                          # data parallel: cuda:LOCAL_RANK before anything is allocated
-    UF.set_compute_dtype(torch.bfloat16 if args.dtype == "bf16" else torch.float32)
-    UF.set_dropout_seed(args.seed + 7919 * rank)                # ranks draw different dropout masks, like different micro-batches
-    model, tokenizer = prepare_model(args)
-    model.train()
-    logging.info(model_summary({"model": model}))
-    criterion = InfoNCELoss(temperature=args.temperature)
-    opt = FlatAdapterOptimizer([(n, p) for n, p in model.named_parameters() if p.requires_grad], lr=args.lr,
-                               betas=(args.beta1_adam, args.beta2_adam), weight_decay=args.weight_decay, max_norm=args.grad_clip)
-    if world > 1:
-        init_data_parallel(opt)
-    updates_per_epoch = math.ceil(len(trainloader) / args.accumulation_steps)
-    total_updates = updates_per_epoch * args.epochs
-    logging.info(f"Gradient accumulation steps: {args.accumulation_steps}; updates per epoch: {updates_per_epoch}; world: {world}")
-    loop = ContrastiveLoop(model, criterion, opt, accumulation_steps=args.accumulation_steps, lr=args.lr, lr_min=args.lr_min, total_updates=total_updates)
-    train_pf = DevicePrefetcher(trainloader, tokenizer, args.device)
-    val_pf = DevicePrefetcher(valloader, tokenizer, args.device)
-
-    best_loss, best_epoch, patience = float("inf"), 0, 0
-    avg_train, update_count, epoch_ms = 0.0, 0, []
-    dm.set_epoch(0)
-    batches = iter(train_pf)                                    # the producer starts now: the first batches are resident when the epoch begins
-    for epoch in range(args.epochs):
-        model.train()
-        loop.begin_epoch(len(trainloader))
-        torch.cuda.synchronize()
-        t0, w0, enq, gw0 = time.perf_counter(), train_pf.wait_s, 0.0, getattr(opt, "gpu_wait_s", 0.0) + UF._STATE.get("gpu_wait_s", 0.0)
-        for batch_idx, (images, tokens, ready) in enumerate(batches):
-            t1 = time.perf_counter()
-            loop.micro(images, tokens, batch_idx, ready=ready)
-            enq += time.perf_counter() - t1
-        t2 = time.perf_counter()
-        g = loop.end_epoch()                                     # the epoch's one host read (reference: loss.item() per batch, :290)
-        epoch_ms.append({"ms": (time.perf_counter() - t0) * 1e3, "updates": g["updates"] - update_count, "batches": len(trainloader),
-                         "loader_wait_ms": (train_pf.wait_s - w0) * 1e3, "enqueue_ms": enq * 1e3, "drain_ms": (time.perf_counter() - t2) * 1e3,
-                         "host_waited_for_gpu_ms": (getattr(opt, "gpu_wait_s", 0.0) + UF._STATE.get("gpu_wait_s", 0.0) - gw0) * 1e3})
-        update_count = g["updates"]
-        for i in g["skipped_batches"]:
-            logging.warning(f"Non-finite loss detected at batch {i} in epoch {epoch + 1}, skipping batch")
-        ep_loss, ep_n = g["loss_sum"], g["epoch_accumulated"]
-        if epoch + 1 < args.epochs:                              # next epoch's first batches load while this epoch validates
-            dm.set_epoch(epoch + 1)
-            batches = iter(train_pf)
-        model.eval()
-        vstat = torch.zeros(2, device=args.device)
-        with torch.no_grad():
-            for images, tokens, ready in val_pf:
-                torch.cuda.current_stream().wait_event(ready)
-                loss = criterion(model.encode_image(images), model.encode_text(tokens))
-                ok = torch.isfinite(loss)
-                vstat += torch.stack([torch.where(ok, loss, torch.zeros_like(loss)), ok.to(loss.dtype)])
-        val_loss, val_n = vstat.tolist()
-        # every rank evaluated its own shard: the epoch's figures are the sums over ranks, so that the checkpoint / patience /
-        # early-stop decisions below are identical on every rank (a rank that stopped alone would strand the others)
-        val_loss, val_n, ep_loss, ep_n = sum_over_ranks(val_loss, val_n, ep_loss, ep_n)
-        avg_val, avg_train = (val_loss / val_n if val_n else 0.0), (ep_loss / ep_n if ep_n else 0.0)
-        if avg_val < best_loss:
-            best_loss, patience, best_epoch = avg_val, 0, epoch
-            if rank == 0:
-                _save_checkpoint(model, args, os.path.join(args.train_snapshot_path, "best_model.pth"))
-            logging.info(f"\nBest model saved at epoch {epoch + 1} with validation loss {best_loss:.4f}")
-        else:
-            patience += 1
-        logging.info(f"Epoch {epoch + 1}: Train={avg_train:.4f}, Val={avg_val:.4f}, Best={best_loss:.4f}")
-        if patience >= args.patience:
-            logging.info(f"\nEarly stopping at epoch {epoch + 1} as validation loss did not improve for {args.patience} epochs.")
-            break
-    logging.info(f"\n✓ Training completed! Best validation loss: {best_loss:.4f} at epoch {best_epoch + 1}")
-    train_pf.close()                                           # an epoch prefetched ahead and abandoned by early stopping (ADVICE r05)
-    val_pf.close()
-    dm.shutdown()
-    if world > 1:
-        from uia_hip import ops
-        import torch.distributed as dist
-        dist.barrier()
-        ops.comm_destroy()
-    return {"best_val": best_loss, "updates": update_count, "last_train": avg_train, "rank": rank, "world": world, "epochs": epoch_ms}
+    return contrastive.train(args, RECIPE, prepare_model, make_tokenizer)
 
 
 def main(argv=None):
-    args = get_args(argv)
-    random.seed(args.seed)
-    np.random.seed(args.seed)
-    torch.manual_seed(args.seed)
-    args.train_snapshot_path = f"runs/{args.exp}"
-    os.makedirs(args.train_snapshot_path, exist_ok=True)
-    setup_logging(args, args.train_snapshot_path)
-    out = train(args)
-    if args.stats_json and out.get("rank", 0) == 0:
-        import json
-        with open(args.stats_json, "w") as f:
-            json.dump(out, f)
-    return out
+    return contrastive.run(get_args(argv), RECIPE, prepare_model, make_tokenizer)
 
 
 if __name__ == "__main__":

@@ -25,8 +25,8 @@ sys.path.insert(0, str(Path(__file__).resolve().parents[3]))
 import torch
 
 from src.adapters import inject_lora_to_biomedclip, inject_mona_variant_to_open_clip
+from src.adapters.checkpoint import load_adapter_by_name
 from src.datasets.rocov2 import ROCOv2DataModule
-from src.models.biomedclip.zero_shot import load_adapter_by_name
 from src.third_party.biomedclip.model import SyntheticTokenizer, create_biomedclip
 from src.utils.retrieval_metrics import compute_retrieval_metrics, hit_at_k, log_retrieval_metrics, retrieve_topk, write_topk_csv
 from src.utils.tools import default_device, parse_config, setup_logging

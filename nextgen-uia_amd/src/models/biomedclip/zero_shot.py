@@ -20,11 +20,11 @@ sys.path.insert(0, str(Path(__file__).resolve().parents[3]))
 import torch
 
 from src.adapters import inject_lora_to_biomedclip, inject_mona_variant_to_open_clip
+from src.adapters.checkpoint import load_adapter_by_name
 from src.models import zero_shot_eval as ZS
 from src.models.zero_shot_prompt import ensemble_for  # noqa: F401  (the ensembles are part of this module's surface)
 from src.third_party.biomedclip.model import SyntheticTokenizer, create_biomedclip
 from src.utils.tools import parse_config
-from uia_hip import functional as UF
 
 LESION_TYPES = ("benign", "malignant")
 
@@ -59,22 +59,6 @@ def get_args(argv=None):
     p.add_argument("--ckpt_path", type=str, default=None)
     p.add_argument("--model_config", type=str, default=None)
     return p.parse_args(argv)
-
-
-def load_adapter_by_name(model, path, wrapper_key):
-    """reference :107-119 / :136-147: copy every checkpoint tensor whose name exists in the model; at least one must."""
-    ckpt = torch.load(path, map_location="cpu", weights_only=True)
-    state = ckpt.get(wrapper_key, ckpt)
-    model_dict = model.state_dict()
-    loaded = 0
-    for name, param in state.items():
-        if name in model_dict:
-            model_dict[name] = param
-            loaded += 1
-    assert loaded > 0, f"No adapter parameters loaded from {path}"
-    model.load_state_dict(model_dict)
-    UF.WEIGHTS.bump()                                   # operand copies of the replaced weights are stale
-    return loaded
 
 
 def prepare_model(args):

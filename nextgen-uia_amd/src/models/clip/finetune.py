@@ -1,9 +1,9 @@
 """OpenAI-CLIP contrastive fine-tuning with Mona adapters on the MI355X HIP path — drop-in for /root/reference/src/models/clip/finetune.py.
 
 Same command line (every flag and default of reference :27-62: default --mona_variant noise_aware, --ckpt ckpt/ViT-B-16.pt, batch 64, 1000 epochs, no accumulation) and the
-reference's loop (:92-215), which is the MetaCLIP entry point's loop verbatim — per batch InfoNCE on L2-normalised features, non-finite batches skipped with their update,
+reference's loop (:92-215), which is its MetaCLIP entry point's loop verbatim — per batch InfoNCE on L2-normalised features, non-finite batches skipped with their update,
 clip_grad_norm_(1.0) -> AdamW -> cosine LR every iteration, eval-mode validation per epoch, best-val checkpoint of the "mona" parameters, early stopping — so it runs on
-src.models.metaclip.finetune.train (engine.ContrastiveLoop: the measured step, no host read per batch) with this family's model preparation (:65-89): the OpenAI-layout CLIP of
+src/models/contrastive.py with its CLIP_FAMILY recipe (engine.ContrastiveLoop: the measured step, no host read per batch) with this family's model preparation (:65-89): the OpenAI-layout CLIP of
 src/third_party/openai_clip/model.py (sequence-first blocks, nn.MultiheadAttention names, QuickGELU, eps 1e-5) + inject_mona_variant_to_clip.
 
 Differences forced by the build image: `clip.load` (torchvision transforms, the BPE vocabulary file) is not available — --ckpt is read as an OpenAI TorchScript archive or a
@@ -11,21 +11,17 @@ plain state dict when the file exists, otherwise the ViT-B/16 geometry is random
 <start>/<end> ids of the CLIP vocabulary).  Added, non-breaking: --dtype, --synthetic / --data_pt, --model_config, data parallelism under torch.distributed.run, and --zero_shot_eval (the reference's
 run_zero_shot_evaluation, :239, opt-in here: src/models/clip/zero_shot.py once per dataset, each a fresh child process)."""
 import argparse
-import os
-import random
+import dataclasses
 import sys
 from pathlib import Path
 
 sys.path.insert(0, str(Path(__file__).resolve().parents[3]))
 
-import numpy as np
-import torch
-
 from src.adapters import inject_mona_variant_to_clip
-from src.models.metaclip import finetune as _loop
+from src.models import contrastive
 from src.third_party.open_clip.model import SyntheticClipTokenizer
 from src.third_party.openai_clip.model import load_clip
-from src.utils.tools import default_device, parse_config, setup_logging
+from src.utils.tools import default_device, parse_config
 
 
 def get_args(argv=None):
@@ -52,13 +48,8 @@ def get_args(argv=None):
     p.add_argument("--device", type=str, default=default_device())       # decided without a HIP call: the loader workers fork first
     p.add_argument("--patience", type=int, default=10)
     # additions of this build
-    p.add_argument("--dtype", type=str, default="bf16", choices=["bf16", "fp32"])
-    p.add_argument("--synthetic", action="store_true")
-    p.add_argument("--synthetic_train", type=int, default=512)
-    p.add_argument("--synthetic_val", type=int, default=128)
-    p.add_argument("--data_pt", type=str, default=None)
-    p.add_argument("--model_config", type=str, default=None, help="python literal: positional arguments of src.third_party.openai_clip.model.CLIP (tests)")
-    _loop.add_zero_shot_flags(p)
+    contrastive.add_build_args(p)
+    contrastive.add_zero_shot_flags(p)
     return p.parse_args(argv)
 
 
@@ -85,22 +76,16 @@ def prepare_model(args):
     return model, make_tokenizer(args)
 
 
+RECIPE = dataclasses.replace(contrastive.CLIP_FAMILY, zero_shot_script=Path(__file__).parent / "zero_shot.py",
+                             zero_shot_flags=lambda args: ["--ckpt", args.ckpt])              # the reference passes --ckpt on too
+
+
 def train(args):
-    return _loop.train(args, prepare=prepare_model, tokenizer_of=make_tokenizer)
+    return contrastive.train(args, RECIPE, prepare_model, make_tokenizer)
 
 
 def main(argv=None):
-    args = get_args(argv)
-    random.seed(args.seed)
-    np.random.seed(args.seed)
-    torch.manual_seed(args.seed)
-    args.train_snapshot_path = f"runs/{args.exp}"
-    os.makedirs(args.train_snapshot_path, exist_ok=True)
-    setup_logging(args, args.train_snapshot_path)
-    out = train(args)
-    if args.zero_shot_eval:
-        out["zero_shot"] = _loop.run_zero_shot_evaluation(args, script=Path(__file__).parent / "zero_shot.py", extra=["--ckpt", args.ckpt])      # the reference passes --ckpt on too
-    return out
+    return contrastive.run(get_args(argv), RECIPE, prepare_model, make_tokenizer)
 
 
 if __name__ == "__main__":

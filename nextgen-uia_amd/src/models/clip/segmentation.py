@@ -17,8 +17,8 @@ sys.path.insert(0, str(Path(__file__).resolve().parents[3]))
 import torch
 
 from src.adapters import inject_lora_to_clip, inject_mona_variant_to_clip
+from src.adapters.checkpoint import load_adapter_by_name
 from src.models import supervised
-from src.models.biomedclip.zero_shot import load_adapter_by_name
 from src.models.clip.finetune import _geometry
 from src.third_party.openai_clip.clip_adapter import CLIPAdapter
 from src.third_party.openai_clip.model import load_clip

@@ -17,11 +17,11 @@ sys.path.insert(0, str(Path(__file__).resolve().parents[3]))
 import torch
 
 from src.adapters import inject_mona_variant_to_clip
+from src.adapters.checkpoint import load_adapter_by_name
 from src.models import zero_shot_eval as ZS
 from src.models.clip.finetune import _geometry, make_tokenizer
 from src.third_party.openai_clip.model import load_clip
 from src.utils.tools import default_device
-from uia_hip import functional as UF
 
 
 def get_args(argv=None):
@@ -51,28 +51,13 @@ def get_args(argv=None):
     return p.parse_args(argv)
 
 
-def load_mona_by_name(model, path):
-    """reference :125-139: copy every checkpoint tensor whose name exists in the model; at least one must."""
-    state = torch.load(path, map_location="cpu", weights_only=True)
-    model_dict = model.state_dict()
-    loaded = 0
-    for name, param in state.items():
-        if name in model_dict:
-            model_dict[name] = param
-            loaded += 1
-    assert loaded > 0, "No MONA parameters loaded"
-    model.load_state_dict(model_dict)
-    UF.WEIGHTS.bump()                                   # operand copies of the replaced weights are stale
-    return loaded
-
-
 def prepare_model(args):
     logging.info("Loading CLIP model")
     model = load_clip(args.ckpt_path or args.ckpt, _geometry(args), args.seed)
     model.float()
     if args.mona_weights:
         model, mona_count = inject_mona_variant_to_clip(model, variant=args.mona_variant, bottleneck_dim=args.mona_bottleneck, num_layers=args.mona_layers)
-        n = load_mona_by_name(model, args.mona_weights)
+        n = load_adapter_by_name(model, args.mona_weights)       # reference :125-139: a bare dict of tensors, no wrapper key
         logging.info(f"✓ Loaded {n} pretrained MONA parameters from {args.mona_weights}")
     for p in model.parameters():
         p.requires_grad = False

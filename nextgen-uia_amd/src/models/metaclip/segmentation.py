@@ -15,8 +15,8 @@ sys.path.insert(0, str(Path(__file__).resolve().parents[3]))
 import torch
 
 from src.adapters import inject_mona_variant_to_open_clip
+from src.adapters.checkpoint import load_adapter_by_name
 from src.models import supervised
-from src.models.biomedclip.zero_shot import load_adapter_by_name
 from src.third_party.open_clip.model import create_metaclip
 from src.third_party.timm.clip_adapter import TimmCLIPAdapter
 from src.utils.tools import default_device, parse_config

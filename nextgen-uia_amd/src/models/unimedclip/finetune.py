@@ -1,7 +1,7 @@
 """UniMed-CLIP contrastive fine-tuning with Mona adapters on the MI355X HIP path — drop-in for /root/reference/src/models/unimedclip/finetune.py.
 
 Same command line (every flag and default of reference :27-63: --version ViT-B-16-quickgelu, --ckpt ckpt/unimed_clip_vit_b16.pt, default --mona_variant noise_aware, batch 64,
-1000 epochs) and the reference's loop (:111-305), which is the MetaCLIP entry point's loop verbatim — so it runs on src.models.metaclip.finetune.train (engine.ContrastiveLoop: the
+1000 epochs) and the reference's loop (:111-305), which is its MetaCLIP entry point's loop verbatim — so it runs on src/models/contrastive.py with its CLIP_FAMILY recipe (engine.ContrastiveLoop: the
 measured step) with this family's model preparation (:66-108):
   * open_clip's NATIVE ViT-B/16 (QuickGELU forced, :68-73) — src/third_party/open_clip/model.NativeCLIP: batch-first blocks under visual.transformer.resblocks, image_size /
     patch_size / grid_size on the tower, the case-2 branch of inject_mona_variant_to_open_clip (mona.py:633-676);
@@ -13,22 +13,21 @@ tokenised by the deterministic BERT-style stand-in (CLS 2, SEP 3, ids 1000-30000
 Added, non-breaking: --dtype, --synthetic / --data_pt, --model_config, data parallelism under torch.distributed.run, and --zero_shot_eval (the reference's
 run_zero_shot_evaluation, opt-in here: src/models/unimedclip/zero_shot.py once per dataset, each a fresh child process, on the --version / --ckpt trained on)."""
 import argparse
+import dataclasses
 import logging
 import os
-import random
 import sys
 from pathlib import Path
 
 sys.path.insert(0, str(Path(__file__).resolve().parents[3]))
 
-import numpy as np
 import torch
 
 from src.adapters import inject_mona_variant_to_open_clip
-from src.models.metaclip import finetune as _loop
+from src.models import contrastive
 from src.third_party.biomedclip.model import SyntheticTokenizer
 from src.third_party.open_clip.model import create_native_clip
-from src.utils.tools import default_device, parse_config, setup_logging
+from src.utils.tools import default_device, parse_config
 
 
 def get_args(argv=None):
@@ -56,13 +55,8 @@ def get_args(argv=None):
     p.add_argument("--device", type=str, default=default_device())       # decided without a HIP call: the loader workers fork first
     p.add_argument("--patience", type=int, default=10)
     # additions of this build
-    p.add_argument("--dtype", type=str, default="bf16", choices=["bf16", "fp32"])
-    p.add_argument("--synthetic", action="store_true")
-    p.add_argument("--synthetic_train", type=int, default=512)
-    p.add_argument("--synthetic_val", type=int, default=128)
-    p.add_argument("--data_pt", type=str, default=None)
-    p.add_argument("--model_config", type=str, default=None, help="python dict literal: keyword arguments of src.third_party.open_clip.model.NativeCLIP (tests)")
-    _loop.add_zero_shot_flags(p)
+    contrastive.add_build_args(p)
+    contrastive.add_zero_shot_flags(p)
     return p.parse_args(argv)
 
 
@@ -98,22 +92,16 @@ def prepare_model(args):
     return model, make_tokenizer(args)
 
 
+RECIPE = dataclasses.replace(contrastive.CLIP_FAMILY, zero_shot_script=Path(__file__).parent / "zero_shot.py",
+                             zero_shot_flags=lambda args: ["--version", args.version, "--ckpt", args.ckpt])
+
+
 def train(args):
-    return _loop.train(args, prepare=prepare_model, tokenizer_of=make_tokenizer)
+    return contrastive.train(args, RECIPE, prepare_model, make_tokenizer)
 
 
 def main(argv=None):
-    args = get_args(argv)
-    random.seed(args.seed)
-    np.random.seed(args.seed)
-    torch.manual_seed(args.seed)
-    args.train_snapshot_path = f"runs/{args.exp}"
-    os.makedirs(args.train_snapshot_path, exist_ok=True)
-    setup_logging(args, args.train_snapshot_path)
-    out = train(args)
-    if args.zero_shot_eval:
-        out["zero_shot"] = _loop.run_zero_shot_evaluation(args, script=Path(__file__).parent / "zero_shot.py", extra=["--version", args.version, "--ckpt", args.ckpt])
-    return out
+    return contrastive.run(get_args(argv), RECIPE, prepare_model, make_tokenizer)
 
 
 if __name__ == "__main__":

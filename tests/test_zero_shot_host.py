@@ -69,11 +69,13 @@ def test_zero_shot_eval_is_off_by_default_on_the_finetune_entries(family):
 def test_a_failed_child_ends_the_post_training_evaluation(tmp_path, monkeypatch):
     """run_zero_shot_evaluation: a fresh child per dataset (sys.executable, a timeout); the first failure is logged and no further dataset is started."""
     import subprocess
-    from src.models.metaclip import finetune as F
+    from src.models import contrastive as F
+    from src.models.metaclip import finetune as entry
+    script = entry.RECIPE.zero_shot_script
     monkeypatch.chdir(tmp_path)
-    args = F.get_args(["--exp", "x", "--synthetic", "--zero_shot_eval", "--zero_shot_timeout", "7"])
+    args = entry.get_args(["--exp", "x", "--synthetic", "--zero_shot_eval", "--zero_shot_timeout", "7"])
     args.train_snapshot_path = str(tmp_path)
-    assert F.run_zero_shot_evaluation(args) == []                            # no best_model.pth: nothing is started
+    assert F.run_zero_shot_evaluation(args, script) == []                    # no best_model.pth: nothing is started
     torch.save({}, tmp_path / "best_model.pth")
     calls = []
 
@@ -82,7 +84,7 @@ def test_a_failed_child_ends_the_post_training_evaluation(tmp_path, monkeypatch)
         return subprocess.CompletedProcess(cmd, 0 if len(calls) == 1 else 3, stdout="", stderr="boom")
 
     monkeypatch.setattr(F.subprocess, "run", fake_run)
-    assert F.run_zero_shot_evaluation(args, extra=["--ckpt_path", "w.pt"]) == ["LN-INT"]
+    assert F.run_zero_shot_evaluation(args, script, extra=["--ckpt_path", "w.pt"]) == ["LN-INT"]
     assert len(calls) == 2                                                   # LN-EXT failed: BUSI is never started
     cmd, kw = calls[0]
     assert cmd[0] == sys.executable and cmd[1].endswith(os.path.join("metaclip", "zero_shot.py")) and kw["timeout"] == 7
@@ -97,7 +99,7 @@ def test_a_failed_child_ends_the_post_training_evaluation(tmp_path, monkeypatch)
 
     del calls[:]
     monkeypatch.setattr(F.subprocess, "run", slow_run)
-    assert F.run_zero_shot_evaluation(args) == [] and len(calls) == 1
+    assert F.run_zero_shot_evaluation(args, script) == [] and len(calls) == 1
 
 
 # ------------------------------------------------------------------------------------------------ the ROC restatement
