@@ -576,6 +576,26 @@ int uia_augment_batch(void* stream, int B, int S, const float* images, const uin
 int uia_augment_gather(void* stream, int N, int B, int S, int src_dtype, const void* images, const uint8_t* masks, const int32_t* programs, void* ws,
                        size_t ws_bytes, float* out_images, uint8_t* out_masks);
 
+/* `Image.resize` of a batch of decoded images of different sizes, one launch, equal to Pillow 12.2 in every byte (csrc/resize.hip; the arithmetic
+ * in plain Python: src/datasets/pil_resize.py).  src: B images back to back in one DEVICE byte buffer of src_bytes bytes (< 2^31), 8 bits per channel, C in
+ * {1, 3} interleaved channels, at arbitrary byte offsets (read a byte at a time: no alignment is asked).  desc: a HOST array int32 [B][8], per image
+ * (offset, H, W, mask_offset or -1, dst_h, dst_w, y0, x0): the H x W image at `offset` is resampled to dst_h x dst_w and the S x S window at (y0, x0)
+ * of that result is written to out_images fp32 [B,C,S,S] (planar) as (float)q / 255.0f.  The square squash of the reference's supervised loaders is
+ * dst_h = dst_w = S, y0 = x0 = 0; Resize(S) + CenterCrop(S) of its contrastive loader is the window form with C = 3.  Images: Pillow's two-pass
+ * fixed-point resample with the antialiased bicubic filter (a = -0.5; float64 coefficients normalised in tap order and rounded to 22 bits,
+ * clip8((2^21 + sum p k) >> 22), columns first with an 8-bit intermediate, a pass whose axis keeps its size skipped).  Masks: one byte per pixel, H x W, at
+ * mask_offset; Pillow's nearest scaler (source index int(xo), xo = a / 2 stepped by a = in / dst in float64), written to out_masks uint8 [B,1,S,S] as
+ * source byte != 0; an image without a mask gets zeros; out_masks may be NULL when no image has a mask.  Checked before anything is enqueued (non-zero,
+ * nothing written, the image's index in uia_last_error()): 1 <= B <= 65535, 8 <= S <= 1024, C in {1, 3}, H, W >= 1, image and mask inside src,
+ * 1 <= dst_h, dst_w <= 16384, the window inside dst, at most 129 taps per pixel on both axes (2 ceil(2 max(in / dst, 1)) + 1: a downscale of at most
+ * 32x), out_masks given when an image has a mask, outputs that overlap neither src nor each other.  The descriptor is then copied to the workspace with
+ * hipMemcpyAsync on `stream`, so a pinned descriptor must stay as it is until that copy has run.  Asynchronous, deterministic (no atomics).
+ * ws: uia_resize_workspace_bytes(B) of 4-byte aligned scratch (0 for a B outside the limits): the device copy of the descriptor; the 8-bit
+ * intermediate lives in LDS. */
+size_t uia_resize_workspace_bytes(int B);
+int uia_resize_batch(void* stream, int B, int C, int S, const uint8_t* src, size_t src_bytes, const int32_t* desc, void* ws, size_t ws_bytes, float* out_images,
+                     uint8_t* out_masks);
+
 /* ---------------------------------------------------------------------------------------------
  * Layout helpers around the GEMMs. */
 int uia_cast(void* stream, int dtype, size_t n, const float* src, void* dst, float scale);          /* dst = T(scale*src) */

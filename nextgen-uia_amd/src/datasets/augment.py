@@ -150,10 +150,12 @@ class BatchAugmenter:
 
 
 def stage_for(args, with_mask, rank=0):
-    """The training loops' switch: a BatchAugmenter when a flag is on and the data comes from --data_pt (the DataModules take it before --synthetic),
+    """The training loops' switch: a BatchAugmenter when a flag is on and the data comes from --data_pt (the DataModules take it before --synthetic) or
+    from --data_root (taken after both),
     else None — runs on the `--synthetic` noise (timing and tests) and `--no-strong_augs --no-weak_augs` bypass the stage entirely: no launch, the same
     bits as without it.  The stage takes square images of 8 to 1024 pixels a side in [0, 1] (BatchAugmenter refuses other shapes at the first batch)."""
     strong, weak = bool(getattr(args, "strong_augs", False)), bool(getattr(args, "weak_augs", False))
-    if not (strong or weak) or not getattr(args, "data_pt", None):
+    folders = getattr(args, "data_root", None) and not getattr(args, "synthetic", False)      # src/datasets/folder.py: its ResizeStage yields a --data_pt batch
+    if not (strong or weak) or not (getattr(args, "data_pt", None) or folders):
         return None
     return BatchAugmenter(strong, weak, with_mask, getattr(args, "seed", 0), rank)

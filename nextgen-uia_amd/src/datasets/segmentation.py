@@ -2,10 +2,11 @@
 
 The reference reads PNG pairs listed in ../data/NextGen-UIA/segmentation/<dataset>/{train,val,test}.txt with PIL, augments them with torchvision (:14-156) and
 hands batches of (image float32 [B, 3, S, S] in [0, 1] — ONE grayscale channel repeated three times, :175, :199-200 — label float32 [B, 1, S, S] in {0, 1},
-file names) to the loop, `shuffle=True, drop_last=True` for training and neither for validation / test (:223-251).  PIL / torchvision I/O is host-side work
-outside the hot path (and absent from the build image); what the hot path needs is that batch contract and the three splits.  The augmentation (:14-156,
+file names) to the loop, `shuffle=True, drop_last=True` for training and neither for validation / test (:223-251).  `--data_root DIR` reads those folders as
+they are (src/datasets/folder.py: the workers decode, PIL's resize runs on the device, one launch per batch, equal to PIL in every byte) and yields the batch
+a `--data_pt` file of the same pictures yields; this module serves `--synthetic` and `--data_pt`: that batch contract and the three splits.  The augmentation (:14-156,
 `--strong_augs` / `--weak_augs`) is not done here: `__getitem__` returns the plain sample, and the training loops run it on the device on the copied batch
-(src/datasets/augment.py: decisions on the host, pixels in one launch per batch; `--data_pt` batches only).  With a flag on (the default) a `--data_pt` file must hold SQUARE images of 8 to 1024 pixels a side
+(src/datasets/augment.py: decisions on the host, pixels in one launch per batch; `--data_pt` and `--data_root` batches only).  With a flag on (the default) a `--data_pt` file must hold SQUARE images of 8 to 1024 pixels a side
 (anything else is refused at the first training batch: resize the file or pass `--no-strong_augs --no-weak_augs`), and float images are taken to lie in
 [0, 1]: an augmented sample is quantised to 8 bits, which clamps values outside it, while an untouched sample of the same batch passes as it is.  `--synthetic`
 supplies them deterministically (U[0,1) grayscale images with a random-ellipse mask); `--data_pt` takes real data as a .pt file of
@@ -170,7 +171,7 @@ class DataModule:
             self.val_dataset = SyntheticSegmentation(args.synthetic_val, args.img_size, args.seed + 1, "val")
             self.test_dataset = SyntheticSegmentation(args.synthetic_test, args.img_size, args.seed + 2, "test")
         else:
-            raise RuntimeError("no dataset: pass --synthetic or --data_pt (the reference's PIL/torchvision loaders read ../data/NextGen-UIA and are outside this build)")
+            raise RuntimeError("no dataset: pass --synthetic, --data_pt or --data_root (the reference's folders, ../data/NextGen-UIA there, are read by src/datasets/folder.py)")
         self.train_sampler = None
         self._loaders = []
 

@@ -71,6 +71,7 @@ def get_args(argv=None):
     parser.add_argument("--synthetic", action="store_true")
     parser.add_argument("--synthetic_test", type=int, default=64, help="pairs per split of --synthetic")
     parser.add_argument("--data_pt", type=str, default=None, help=".pt with {'images': [N,1|3,S,S], 'captions': [N] str}")
+    parser.add_argument("--data_root", type=str, default=None, help="refused here: the folder loader serves the supervised classification / segmentation entries")
     parser.add_argument("--ckpt_path", type=str, default=None, help="pretrained BiomedCLIP state dict (the reference downloads it by --model_name)")
     parser.add_argument("--model_config", type=str, default=None)
     parser.add_argument("--topk", type=int, default=0, help="list each query's K best candidates (topk_i2t.csv, topk_t2i.csv); 0 = off, at most 32")
@@ -211,6 +212,8 @@ def save_results(args, metrics, image_features=None, text_features=None, caption
 
 def main(argv=None):
     args = get_args(argv)
+    from src.datasets import folder
+    folder.refuse(args, "retrieval")
     if args.output_dir is None:
         args.output_dir = f"runs/{args.exp}/test"
     os.makedirs(args.output_dir, exist_ok=True)

@@ -55,6 +55,7 @@ def get_args(argv=None):
     p.add_argument("--synthetic", action="store_true")
     p.add_argument("--synthetic_test", type=int, default=64)
     p.add_argument("--data_pt", type=str, default=None, help=".pt with {'images': [N,3,S,S], 'labels': [N]}")
+    p.add_argument("--data_root", type=str, default=None, help="refused here: the folder loader serves the supervised classification / segmentation entries")
     p.add_argument("--prompts_json", type=str, default=None, help='{"benign": [...], "malignant": [...]}')
     p.add_argument("--ckpt_path", type=str, default=None)
     p.add_argument("--model_config", type=str, default=None)

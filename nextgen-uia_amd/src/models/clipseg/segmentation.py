@@ -32,6 +32,7 @@ sys.path.insert(0, str(Path(__file__).resolve().parents[3]))
 
 import torch
 
+from src.datasets import folder as dataset_folder
 from src.datasets.segmentation import synthetic_batch      # noqa: F401  (bench.py and tools import it from here)
 from src.models import supervised
 from src.models.clipseg.prompt import busi_prompt, ln_prompt, prostate_prompt, thyroid_prompt
@@ -144,7 +145,8 @@ def prepare_model(args):
 
 
 def check_args(args):
-    """The refusal, before any allocation."""
+    """The refusals, before any allocation."""
+    dataset_folder.refuse(args, "the CLIPSeg loop")
     if get_prompt(args) is None:
         raise ValueError(f"no prompt for --dataset {args.dataset} (LN-INT, LN-EXT, BUSI, DDTI, TN3K, Prostate; reference get_prompt returns None and fails at .repeat)")
 

@@ -92,6 +92,7 @@ def add_build_args(p):
     p.add_argument("--synthetic_train", type=int, default=512)
     p.add_argument("--synthetic_val", type=int, default=128)
     p.add_argument("--data_pt", type=str, default=None, help=".pt with {'images': [N,3,S,S], 'texts': [str]}")
+    p.add_argument("--data_root", type=str, default=None, help="refused here: the folder loader serves the supervised classification / segmentation entries")
     p.add_argument("--model_config", type=str, default=None, help="python literal overriding the model geometry, in the form the family's model constructor takes (tests)")
 
 
@@ -248,6 +249,8 @@ def run_zero_shot_evaluation(args, script, extra=()):
 
 def run(args, recipe, prepare_model, make_tokenizer):
     """main() of every entry point: seeds, runs/<exp>, train; then --zero_shot_eval and --stats_json (rank 0) where the entry has the flag.  Returns train()'s dict."""
+    from src.datasets import folder
+    folder.refuse(args, "the contrastive fine-tune")
     random.seed(args.seed)
     np.random.seed(args.seed)
     torch.manual_seed(args.seed)

@@ -10,7 +10,8 @@ the results table, results.csv and the backup folder, and for segmentation the r
 (src/utils/viz.py: one launch per batch, written by background threads; --no-viz leaves the folder empty; the test passes inside train() write none); `main`: train unless --test, then ALWAYS test.
 Different on purpose: the iteration is engine.segmentation_step (zero_grad -> forward -> criterion -> backward -> AdamW, nothing read on the host; every
 tenth loss is kept as a device scalar and written at validation time), batches arrive through engine.DevicePrefetcher, --strong_augs / --weak_augs act
-on --data_pt training batches on the device (src/datasets/augment.py), metrics are computed on the device (one host read per split), scalars go to
+on --data_pt training batches on the device (src/datasets/augment.py), --data_root reads the reference's dataset folders (src/datasets/folder.py: the
+workers decode, a ResizeStage ahead of the augmentation makes PIL's resize on the device and yields the --data_pt batch of the same files), metrics are computed on the device (one host read per split), scalars go to
 <train dir>/log/scalars.jsonl.  If no validation ever improves on 0.0 the last iterate is saved, so test() has a checkpoint.
 
 What differs by task is a field of `Task`; what differs by model is an argument: `prepare(args) -> model`, and `forward_kwargs(args) -> (batch size ->
@@ -32,6 +33,7 @@ import torch
 from src.datasets import classification as dataset_cls
 from src.datasets import fewshot_classification as dataset_fs_cls
 from src.datasets import fewshot_segmentation as dataset_fs_seg
+from src.datasets import folder as dataset_folder
 from src.datasets import segmentation as dataset_seg
 from src.datasets.augment import stage_for
 from src.datasets.resident import resident_for
@@ -105,6 +107,8 @@ def add_build_args(p, synthetic_train=256):
     p.add_argument("--synthetic_test", type=int, default=64)
     p.add_argument("--stats_json", type=str, default=None)
     p.add_argument("--data_pt", type=str, default=None)
+    p.add_argument("--data_root", type=str, default=None,
+                   help="the reference's dataset folders (<dir>/{classification,segmentation}/<dataset>/*.txt, <dir>/all/{images,masks}); after --data_pt and --synthetic")
     p.add_argument("--ckpt_path", type=str, default=None, help="backbone state dict (.pt); random init if absent")
     p.add_argument("--model_config", type=str, default=None)
     p.add_argument("--extract_layers", type=str, default="3,6,9", help="transformer blocks tapped by the adapter (reference: fixed 3,6,9)")
@@ -132,15 +136,31 @@ def _bind(args, task):
     UF.set_compute_dtype(torch.bfloat16 if args.dtype == "bf16" else torch.float32)
 
 
-def evaluate(task, model, loader_pf, accumulator, in_channels=3, kwargs_for=_no_kwargs, viz=None, name_of=None):
+def _data_module(args, task, rank, world):
+    """task.data.DataModule, or the folder loader's when --data_root is what the DataModules' precedence picks (src/datasets/folder.py)."""
+    if dataset_folder.chosen(args):
+        return dataset_folder.DataModule(args, "segmentation" if task.with_mask else "classification", rank=rank, world=world)
+    return task.data.DataModule(args, rank=rank, world=world)
+
+
+def _prefetcher(args, task, loader):
+    if dataset_folder.chosen(args):
+        return dataset_folder.RaggedPrefetcher(loader, args.device)
+    return DevicePrefetcher(loader, None, args.device, second=task.data.second_of)
+
+
+def evaluate(task, model, loader_pf, accumulator, in_channels=3, kwargs_for=_no_kwargs, viz=None, name_of=None, resize=None):
     """One pass of a validation / test split.  viz: a src.utils.viz.SegVisualizer that takes every batch behind its metrics, with name_of(i) the file
-    name of sample i of the split (the prefetcher drops names; these loaders do not shuffle, so a running index is the sample's)."""
+    name of sample i of the split (the prefetcher drops names; these loaders do not shuffle, so a running index is the sample's).  resize: the
+    src.datasets.folder.ResizeStage of a --data_root run, which turns the prefetcher's ragged batch into the batch everything below takes."""
     cur = torch.cuda.current_stream()
     to_input = task.to_input
     seen = 0
     with torch.no_grad():
         for images, labels, ready in loader_pf:
             cur.wait_event(ready)
+            if resize is not None:
+                images, labels = resize(images, labels)
             images, labels = to_input(images, labels, in_channels)
             preds = model(images, **kwargs_for(images.shape[0])).detach()
             accumulator.update(preds, labels.detach())
@@ -157,8 +177,8 @@ def _write_roc_csv(accumulator, folder, iter_num):
         f.writelines(f"{a!r},{b!r},{c!r}\n" for a, b, c in zip(fpr, tpr, thr))
 
 
-def _split_pass(task, model, loader_pf, accumulator, args, kwargs_for, writer, split, iter_num, roc_dir=None):
-    evaluate(task, model, loader_pf, accumulator, args.in_channels, kwargs_for)
+def _split_pass(task, model, loader_pf, accumulator, args, kwargs_for, writer, split, iter_num, roc_dir=None, resize=None):
+    evaluate(task, model, loader_pf, accumulator, args.in_channels, kwargs_for, resize=resize)
     stats = accumulator.compute()
     if roc_dir is not None:
         _write_roc_csv(accumulator, roc_dir, iter_num)
@@ -173,7 +193,7 @@ def train(args, task, prepare, forward_kwargs=None):
     rank, _, world = dist_env() if task.data_parallel or task.resident else (0, 0, 1)      # resident: the module refuses a world above 1
     if not torch.cuda.is_initialized():
         torch.set_num_threads(max(1, min(4, torch.get_num_threads())))
-    dm = (task.train_module or task.data.DataModule)(args, rank=rank, world=world)
+    dm = task.train_module(args, rank=rank, world=world) if task.train_module else _data_module(args, task, rank, world)
     if task.resident:
         logging.info(f"Training samples: {dm.sampled_train_count} / {dm.original_train_count}")
     trainloader = None if task.resident else dm.train_dataloader()
@@ -191,9 +211,8 @@ def train(args, task, prepare, forward_kwargs=None):
                                weight_decay=args.weight_decay, max_norm=0.0)              # no clipping in these loops
     if world > 1:
         init_data_parallel(opt)
-    second = task.data.second_of
-    train_pf = resident_for(args, dm, rank) if task.resident else DevicePrefetcher(trainloader, None, args.device, second=second)
-    val_pf, test_pf = (DevicePrefetcher(loader, None, args.device, second=second) for loader in (valloader, testloader))
+    train_pf = resident_for(args, dm, rank) if task.resident else _prefetcher(args, task, trainloader)
+    val_pf, test_pf = (_prefetcher(args, task, loader) for loader in (valloader, testloader))
     max_iters = len(train_pf if task.resident else trainloader) * args.epochs
     best_path = os.path.join(args.train_snapshot_path, "best_model.pth")
     iter_num, best, patience, logged, last = 0, 0.0, 0, [], None
@@ -202,6 +221,7 @@ def train(args, task, prepare, forward_kwargs=None):
     bufs = {}                                                    # a widened training batch lives in the same two tensors every iteration
     # --strong_augs / --weak_augs on --data_pt batches; None: bypassed, or (resident) run by the launch that forms the batch
     augment = None if task.resident else stage_for(args, with_mask=task.with_mask, rank=rank)
+    resize = dataset_folder.stage_for(args, task.with_mask)      # --data_root: PIL's resize of the decoded files, one launch per batch; else None
     criterion, to_input, with_mask, ahead, in_channels = task.criterion, task.to_input, task.with_mask, task.data_parallel, args.in_channels
     lr_max, lr_min, clock = args.lr, args.lr_min, time.perf_counter
     batches = None
@@ -220,6 +240,8 @@ def train(args, task, prepare, forward_kwargs=None):
         for images, labels, ready in batches:
             t1 = clock()
             cur.wait_event(ready)
+            if resize is not None:
+                images, labels = resize(images, labels)
             if augment is not None:
                 images, labels = augment(images, labels) if with_mask else (augment(images)[0], labels)
             images, labels = to_input(images, labels, in_channels, bufs)
@@ -251,7 +273,7 @@ def train(args, task, prepare, forward_kwargs=None):
         logged = []
         accumulator = task.metrics(criterion=criterion, num_classes=args.num_classes)
         roc_dir = os.path.join(args.train_snapshot_path, "roc_curves") if task.roc_csv and rank == 0 else None
-        stats = _split_pass(task, model, val_pf, accumulator, args, kwargs_for, writer, "val", iter_num, roc_dir)
+        stats = _split_pass(task, model, val_pf, accumulator, args, kwargs_for, writer, "val", iter_num, roc_dir, resize)
         val_hist.append({"epoch": epoch, **stats})
         if stats[task.best] > best:
             patience, best = 0, stats[task.best]
@@ -265,7 +287,7 @@ def train(args, task, prepare, forward_kwargs=None):
                 logging.info(f"Early stopping triggered at epoch {epoch + 1}")
             break
         logging.info(f"\titer: {iter_num}, loss: {stats['loss']:.4f}, " + task.line(stats))
-        val_hist[-1]["test"] = _split_pass(task, model, test_pf, accumulator, args, kwargs_for, writer, "test", iter_num)
+        val_hist[-1]["test"] = _split_pass(task, model, test_pf, accumulator, args, kwargs_for, writer, "test", iter_num, resize=resize)
         model.train()
 
     writer.close()
@@ -299,7 +321,7 @@ def train(args, task, prepare, forward_kwargs=None):
 def test(args, task, prepare, forward_kwargs=None):
     logging.info("Start testing")
     rank = dist_env()[0] if task.data_parallel else 0
-    dm = task.data.DataModule(args, rank=0, world=1)             # every rank evaluates the whole split
+    dm = _data_module(args, task, 0, 1)                          # every rank evaluates the whole split
     testloader = dm.test_dataloader()
     dm.start_workers()
     _bind(args, task)
@@ -315,9 +337,9 @@ def test(args, task, prepare, forward_kwargs=None):
         if task.visualize and getattr(args, "viz", True):
             viz = SegVisualizer(viz_path, args.batch_size, args.img_size)
     accumulator = task.metrics(criterion=task.criterion, num_classes=args.num_classes)
-    test_pf = DevicePrefetcher(testloader, None, args.device, second=task.data.second_of)
+    test_pf = _prefetcher(args, task, testloader)
     try:
-        evaluate(task, model, test_pf, accumulator, args.in_channels, kwargs_for, viz, dm.test_dataset.name_of)
+        evaluate(task, model, test_pf, accumulator, args.in_channels, kwargs_for, viz, dm.test_dataset.name_of, dataset_folder.stage_for(args, task.with_mask))
         stats = accumulator.compute()
     finally:
         if viz is not None:
@@ -331,6 +353,8 @@ def test(args, task, prepare, forward_kwargs=None):
 
 def run(args, task, prepare, forward_kwargs=None):
     """main() of every entry point: seeds, the two run directories, train unless --test, then ALWAYS test.  Returns train()'s dict with test()'s under "test"."""
+    if task.resident:
+        dataset_folder.refuse(args, "a few-shot entry (its training set is resident on the device)")
     random.seed(args.seed)
     np.random.seed(args.seed)
     torch.manual_seed(args.seed)

@@ -37,6 +37,7 @@ def add_build_flags(p):
     p.add_argument("--synthetic", action="store_true")
     p.add_argument("--synthetic_test", type=int, default=64)
     p.add_argument("--data_pt", type=str, default=None, help=".pt with {'images': [N,3,S,S], 'labels': [N]}")
+    p.add_argument("--data_root", type=str, default=None, help="refused here: the folder loader serves the supervised classification / segmentation entries")
     p.add_argument("--prompts_json", type=str, default=None, help='{"benign": [...], "malignant": [...]}')
     p.add_argument("--ckpt_path", type=str, default=None)
     p.add_argument("--model_config", type=str, default=None)
@@ -44,6 +45,8 @@ def add_build_flags(p):
 
 def load_test_split(args):
     """(images float [N,3,S,S], labels int64 [N]) on the host."""
+    from src.datasets import folder
+    folder.refuse(args, "zero-shot classification")
     if args.data_pt:
         blob = torch.load(args.data_pt)
         images, labels = blob["images"], blob["labels"].long()

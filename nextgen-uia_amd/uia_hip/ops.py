@@ -1954,6 +1954,46 @@ def augment_gather(images, masks, programs, out_images=None, out_masks=None, ws=
     return out_images, out_masks
 
 
+# ---------------------------------------------------------------- Pillow's resize of a ragged batch (csrc/resize.hip)
+RESIZE_DESC = 8                            # int32 per image: offset, H, W, mask offset or -1, dst_h, dst_w, y0, x0
+
+
+def resize_workspace(B, device):
+    """The scratch of one uia_resize_batch call on B images (a caller that resizes every batch keeps it)."""
+    need = lib().uia_resize_workspace_bytes(int(B))
+    if need == 0:
+        raise UiaError(f"resize_batch: B={B} is outside the kernel's limits (1 <= B <= 65535)")
+    return torch.empty(need, device=device, dtype=torch.uint8)
+
+
+def resize_batch(src, desc, S, C=1, out_images=None, out_masks=None, ws=None):
+    """src: a 1-D uint8 device tensor holding B decoded images back to back (8 bits per channel, C interleaved channels, any offsets) and their
+    one-byte-per-pixel masks; desc a HOST int32 tensor [B, 8], per image (offset, H, W, mask offset or -1, dst_h, dst_w, y0, x0) (pinned memory makes
+    its copy asynchronous, and it must then stay unchanged until the copy has run) -> (out_images fp32 [B, C, S, S], out_masks uint8 [B, 1, S, S] or
+    None when no image has a mask): every image resampled to dst_h x dst_w as PIL's `Image.resize` does it (antialiased bicubic; masks: nearest), the
+    S x S window at (y0, x0) written as q / 255, in one launch.  Enqueued only.  out_* and ws may be handed in to be reused."""
+    _p(src)
+    if src.dim() != 1 or src.dtype != torch.uint8 or not src.is_contiguous():
+        raise UiaError(f"resize_batch: src must be a contiguous 1-D uint8 tensor, got {src.dtype} {tuple(src.shape)}")
+    if (not isinstance(desc, torch.Tensor) or desc.is_cuda or desc.dtype != torch.int32 or desc.dim() != 2 or desc.shape[1] != RESIZE_DESC
+            or desc.shape[0] < 1 or not desc.is_contiguous()):
+        raise UiaError(f"resize_batch: desc must be a contiguous host int32 tensor [B, {RESIZE_DESC}]")
+    B, S, C = desc.shape[0], int(S), int(C)
+    with_masks = out_masks is not None or bool((desc[:, 3] >= 0).any())
+    if out_images is None:
+        out_images = torch.empty((B, C, S, S), dtype=torch.float32, device=src.device)
+    if with_masks and out_masks is None:
+        out_masks = torch.empty((B, 1, S, S), dtype=torch.uint8, device=src.device)
+    for o, ch, dt, name in ((out_images, C, torch.float32, "out_images"), (out_masks, 1, torch.uint8, "out_masks")):
+        if o is not None and (tuple(o.shape) != (B, ch, S, S) or o.dtype != dt or not o.is_contiguous() or o.device != src.device):
+            raise UiaError(f"resize_batch: {name} must be contiguous {dt} [{B}, {ch}, {S}, {S}] on the source's device")
+    if ws is None:
+        ws = resize_workspace(B, src.device)
+    check(lib().uia_resize_batch(_stream(), B, C, S, _p(src), src.numel(), desc.data_ptr(), _p(ws), ws.numel(), _p(out_images), _p(out_masks)),
+          "uia_resize_batch")
+    return out_images, out_masks
+
+
 # ---------------------------------------------------------------- DINOv2 UNet decoder (csrc/unet_conv.hip, unet_bn.hip, unet_resample.hip)
 CONV3, CONVT_FWD, CONVT_BWD, CONV1 = 0, 1, 2, 3      # uia_conv_igemm / uia_conv_wgrad modes
 BN_SLICES = 256                            # UIA_BN_SLICES
