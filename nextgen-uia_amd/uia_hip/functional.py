@@ -2094,6 +2094,19 @@ def conv3_dgrad_rows(w, dt):
     return w.detach().flip(2, 3).permute(1, 2, 3, 0).reshape(w.shape[1], -1).to(dt).contiguous()
 
 
+def _unet_conv_backward(ctx, x1, x2, w, dy):
+    """The conv part of the two conv + BatchNorm backwards below, from the BatchNorm's dy -> (dx1, dx2, dw, db)"""
+    N, Cin = w.shape[0], w.shape[1]
+    dw = ops.conv_wgrad(ops.CONV3, x1, x2, dy, N).reshape(N, 3, 3, Cin).permute(0, 3, 1, 2).contiguous()
+    db = ops.colsum_ordered(dy)
+    dx1 = dx2 = None
+    if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+        C1 = x1.shape[3]
+        r = ops.conv_igemm(ops.CONV3, dy, None, conv3_dgrad_rows(w, dy.dtype), Cin, n1=C1)
+        dx1, dx2 = (r if x2 is not None else (r, None))
+    return dx1, dx2, dw, db
+
+
 class UnetConvBNReLUFn(torch.autograd.Function):
     """ReLU(BatchNorm2d(Conv2d3x3(cat[x1, x2]) + b)) on NHWC x1 [B,H,W,C1], x2 [B,H,W,C2] (x2 may be None); the concatenation is never
     written.  training: batch statistics, running buffers updated on the device; eval: the running statistics (no backward)."""
@@ -2114,15 +2127,7 @@ class UnetConvBNReLUFn(torch.autograd.Function):
             raise UiaError("UnetConvBNReLUFn: eval-mode BatchNorm has no backward here (the decoder trains in train mode)")
         x1, x2, w, y, gamma, mean, invstd, scale, shift = ctx.saved_tensors
         dy, dgamma, dbeta = ops.bn_relu_bwd(y, dout.contiguous(), scale, shift, mean, invstd, gamma.detach())
-        N, Cin = w.shape[0], w.shape[1]
-        dw = ops.conv_wgrad(ops.CONV3, x1, x2, dy, N).reshape(N, 3, 3, Cin).permute(0, 3, 1, 2).contiguous()
-        db = ops.colsum_ordered(dy)
-        dx1 = dx2 = None
-        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
-            C1 = x1.shape[3]
-            r = ops.conv_igemm(ops.CONV3, dy, None, conv3_dgrad_rows(w, dy.dtype), Cin, n1=C1)
-            dx1, dx2 = (r if x2 is not None else (r, None))
-        return dx1, dx2, dw, db, dgamma, dbeta, None, None, None, None, None, None
+        return (*_unet_conv_backward(ctx, x1, x2, w, dy), dgamma, dbeta, None, None, None, None, None, None)
 
 
 class UnetConvBNActFn(torch.autograd.Function):
@@ -2157,15 +2162,7 @@ class UnetConvBNActFn(torch.autograd.Function):
         x1, x2, w, y, gamma, mean, invstd, scale, shift, keep_mask = ctx.saved_tensors
         slope, drop_p, seed = ctx.act
         dy, dgamma, dbeta = ops.bn_act_bwd(y, dout.contiguous(), scale, shift, mean, invstd, gamma.detach(), slope, drop_p, seed, keep_mask)
-        N, Cin = w.shape[0], w.shape[1]
-        dw = ops.conv_wgrad(ops.CONV3, x1, x2, dy, N).reshape(N, 3, 3, Cin).permute(0, 3, 1, 2).contiguous()
-        db = ops.colsum_ordered(dy)
-        dx1 = dx2 = None
-        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
-            C1 = x1.shape[3]
-            r = ops.conv_igemm(ops.CONV3, dy, None, conv3_dgrad_rows(w, dy.dtype), Cin, n1=C1)
-            dx1, dx2 = (r if x2 is not None else (r, None))
-        return dx1, dx2, dw, db, dgamma, dbeta, None, None, None, None, None, None, None, None, None
+        return (*_unet_conv_backward(ctx, x1, x2, w, dy), dgamma, dbeta, None, None, None, None, None, None, None, None, None)
 
 
 class UnetConvFn(torch.autograd.Function):

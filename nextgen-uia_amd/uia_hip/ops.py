@@ -2088,21 +2088,43 @@ def colsum_ordered(y):
     return out
 
 
-def bn_fwd(y, gamma, beta, running_mean, running_var, num_batches_tracked, training, momentum=0.1, eps=1e-5, relu=True):
-    """BatchNorm2d (+ ReLU) on NHWC y (uia_bn_fwd).  Returns (out, mean, invstd, scale, shift); mean / invstd are None in eval mode.
-    Training updates running_mean / running_var / num_batches_tracked in place (any of them may be None: no update)."""
-    _nhwc(y, "bn_fwd y")
+def _bn_fwd_args(name, y, gamma, beta, running_mean, running_var, num_batches_tracked, training):
+    """What the three BatchNorm forwards share: the checks of y and the per-channel tensors, and the outputs.
+    -> (M, C, out, mean, invstd, scale, shift, ws); mean / invstd / ws are None in eval mode."""
+    _nhwc(y, f"{name} y")
     C = y.shape[3]
     M = y.numel() // C
     for t, nm in ((gamma, "gamma"), (beta, "beta"), (running_mean, "running_mean"), (running_var, "running_var")):
         if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != C):
-            raise UiaError(f"bn_fwd: {nm} must be contiguous fp32 [{C}]")
+            raise UiaError(f"{name}: {nm} must be contiguous fp32 [{C}]")
     if num_batches_tracked is not None and num_batches_tracked.dtype != torch.int64:
-        raise UiaError("bn_fwd: num_batches_tracked must be int64")
+        raise UiaError(f"{name}: num_batches_tracked must be int64")
     f = lambda: torch.empty(C, device=y.device, dtype=torch.float32)   # noqa: E731
     scale, shift = f(), f()
     mean, invstd, ws = (f(), f(), torch.empty(BN_SLICES * C * 3, device=y.device, dtype=torch.float32)) if training else (None, None, None)
-    out = torch.empty_like(y)
+    return M, C, torch.empty_like(y), mean, invstd, scale, shift, ws
+
+
+def _bn_bwd_args(name, y, like, chans):
+    """What the three BatchNorm backwards share: `like` ((tensor, its name), ...) must have y's layout, dtype and shape, `chans` must be
+    per-channel fp32.  -> (M, C, dy, dgamma, dbeta, ws)"""
+    _nhwc(y, f"{name} y")
+    for t, nm in like:
+        _nhwc(t, f"{name} {nm}", y.dtype)
+    if any(t.shape != y.shape for t, _ in like):
+        raise UiaError(f"{name}: {', '.join(nm for _, nm in like)} and y differ in shape")
+    C = y.shape[3]
+    for t, nm in chans:
+        if t is None or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != C:
+            raise UiaError(f"{name}: {nm} must be contiguous fp32 [{C}]")
+    f = lambda: torch.empty(C, device=y.device, dtype=torch.float32)   # noqa: E731
+    return y.numel() // C, C, torch.empty_like(y), f(), f(), torch.empty(BN_SLICES * C * 3, device=y.device, dtype=torch.float32)
+
+
+def bn_fwd(y, gamma, beta, running_mean, running_var, num_batches_tracked, training, momentum=0.1, eps=1e-5, relu=True):
+    """BatchNorm2d (+ ReLU) on NHWC y (uia_bn_fwd).  Returns (out, mean, invstd, scale, shift); mean / invstd are None in eval mode.
+    Training updates running_mean / running_var / num_batches_tracked in place (any of them may be None: no update)."""
+    M, C, out, mean, invstd, scale, shift, ws = _bn_fwd_args("bn_fwd", y, gamma, beta, running_mean, running_var, num_batches_tracked, training)
     check(lib().uia_bn_fwd(_stream(), _code(y.dtype), int(bool(training)), M, C, _p(y), _p(gamma), _p(beta), _p(running_mean), _p(running_var),
                            _p(num_batches_tracked), float(momentum), float(eps), _p(ws), _p(mean), _p(invstd), _p(scale), _p(shift), int(bool(relu)), _p(out)),
           "uia_bn_fwd")
@@ -2111,19 +2133,8 @@ def bn_fwd(y, gamma, beta, running_mean, running_var, num_batches_tracked, train
 
 def bn_relu_bwd(y, dout, scale, shift, mean, invstd, gamma):
     """Backward of train-mode BatchNorm2d + ReLU (uia_bn_relu_bwd): returns (dy, dgamma, dbeta)."""
-    _nhwc(y, "bn_relu_bwd y")
-    _nhwc(dout, "bn_relu_bwd dout", y.dtype)
-    if dout.shape != y.shape:
-        raise UiaError("bn_relu_bwd: dout and y differ in shape")
-    C = y.shape[3]
-    for t, nm in ((scale, "scale"), (shift, "shift"), (mean, "mean"), (invstd, "invstd"), (gamma, "gamma")):
-        if t is None or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != C:
-            raise UiaError(f"bn_relu_bwd: {nm} must be contiguous fp32 [{C}]")
-    M = y.numel() // C
-    ws = torch.empty(BN_SLICES * C * 3, device=y.device, dtype=torch.float32)
-    dgamma = torch.empty(C, device=y.device, dtype=torch.float32)
-    dbeta = torch.empty(C, device=y.device, dtype=torch.float32)
-    dy = torch.empty_like(y)
+    M, C, dy, dgamma, dbeta, ws = _bn_bwd_args("bn_relu_bwd", y, ((dout, "dout"),),
+                                               ((scale, "scale"), (shift, "shift"), (mean, "mean"), (invstd, "invstd"), (gamma, "gamma")))
     check(lib().uia_bn_relu_bwd(_stream(), _code(y.dtype), M, C, _p(y), _p(dout), _p(scale), _p(shift), _p(mean), _p(invstd), _p(gamma), _p(ws),
                                 _p(dgamma), _p(dbeta), _p(dy)), "uia_bn_relu_bwd")
     return dy, dgamma, dbeta
@@ -2151,19 +2162,8 @@ def bn_act_fwd(y, gamma, beta, running_mean, running_var, num_batches_tracked, t
                keep_mask=None):
     """BatchNorm2d + LeakyReLU(slope) + Dropout(drop_p) on NHWC y (uia_bn_act_fwd).  Returns (out, mean, invstd, scale, shift) as bn_fwd does.
     Dropout runs in training only: keep_mask (uint8, y's shape) when given, else the draw of ops.dropout for `seed`."""
-    _nhwc(y, "bn_act_fwd y")
-    C = y.shape[3]
-    M = y.numel() // C
-    for t, nm in ((gamma, "gamma"), (beta, "beta"), (running_mean, "running_mean"), (running_var, "running_var")):
-        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != C):
-            raise UiaError(f"bn_act_fwd: {nm} must be contiguous fp32 [{C}]")
-    if num_batches_tracked is not None and num_batches_tracked.dtype != torch.int64:
-        raise UiaError("bn_act_fwd: num_batches_tracked must be int64")
+    M, C, out, mean, invstd, scale, shift, ws = _bn_fwd_args("bn_act_fwd", y, gamma, beta, running_mean, running_var, num_batches_tracked, training)
     drop_p, keep_mask = _drop_args("bn_act_fwd", y, drop_p, keep_mask, training)
-    f = lambda: torch.empty(C, device=y.device, dtype=torch.float32)   # noqa: E731
-    scale, shift = f(), f()
-    mean, invstd, ws = (f(), f(), torch.empty(BN_SLICES * C * 3, device=y.device, dtype=torch.float32)) if training else (None, None, None)
-    out = torch.empty_like(y)
     check(lib().uia_bn_act_fwd(_stream(), _code(y.dtype), int(bool(training)), M, C, _p(y), _p(gamma), _p(beta), _p(running_mean), _p(running_var),
                                _p(num_batches_tracked), float(momentum), float(eps), _p(ws), _p(mean), _p(invstd), _p(scale), _p(shift), float(slope), _p(out),
                                drop_p, int(seed) & 0xFFFFFFFFFFFFFFFF, _p(keep_mask)), "uia_bn_act_fwd")
@@ -2172,20 +2172,9 @@ def bn_act_fwd(y, gamma, beta, running_mean, running_var, num_batches_tracked, t
 
 def bn_act_bwd(y, dout, scale, shift, mean, invstd, gamma, slope=0.01, drop_p=0.0, seed=0, keep_mask=None):
     """Backward of train-mode bn_act_fwd (uia_bn_act_bwd): returns (dy, dgamma, dbeta)."""
-    _nhwc(y, "bn_act_bwd y")
-    _nhwc(dout, "bn_act_bwd dout", y.dtype)
-    if dout.shape != y.shape:
-        raise UiaError("bn_act_bwd: dout and y differ in shape")
-    C = y.shape[3]
-    for t, nm in ((scale, "scale"), (shift, "shift"), (mean, "mean"), (invstd, "invstd"), (gamma, "gamma")):
-        if t is None or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != C:
-            raise UiaError(f"bn_act_bwd: {nm} must be contiguous fp32 [{C}]")
+    M, C, dy, dgamma, dbeta, ws = _bn_bwd_args("bn_act_bwd", y, ((dout, "dout"),),
+                                               ((scale, "scale"), (shift, "shift"), (mean, "mean"), (invstd, "invstd"), (gamma, "gamma")))
     drop_p, keep_mask = _drop_args("bn_act_bwd", y, drop_p, keep_mask)
-    M = y.numel() // C
-    ws = torch.empty(BN_SLICES * C * 3, device=y.device, dtype=torch.float32)
-    dgamma = torch.empty(C, device=y.device, dtype=torch.float32)
-    dbeta = torch.empty(C, device=y.device, dtype=torch.float32)
-    dy = torch.empty_like(y)
     check(lib().uia_bn_act_bwd(_stream(), _code(y.dtype), M, C, _p(y), _p(dout), _p(scale), _p(shift), _p(mean), _p(invstd), _p(gamma), _p(ws),
                                _p(dgamma), _p(dbeta), _p(dy), float(slope), drop_p, int(seed) & 0xFFFFFFFFFFFFFFFF, _p(keep_mask)), "uia_bn_act_bwd")
     return dy, dgamma, dbeta
@@ -2352,17 +2341,7 @@ def bn_add_relu_fwd(y, r, gamma, beta, running_mean, running_var, num_batches_tr
         _nhwc(r, "bn_add_relu_fwd r", y.dtype)
         if r.shape != y.shape:
             raise UiaError("bn_add_relu_fwd: r and y differ in shape")
-    C = y.shape[3]
-    M = y.numel() // C
-    for t, nm in ((gamma, "gamma"), (beta, "beta"), (running_mean, "running_mean"), (running_var, "running_var")):
-        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != C):
-            raise UiaError(f"bn_add_relu_fwd: {nm} must be contiguous fp32 [{C}]")
-    if num_batches_tracked is not None and num_batches_tracked.dtype != torch.int64:
-        raise UiaError("bn_add_relu_fwd: num_batches_tracked must be int64")
-    f = lambda: torch.empty(C, device=y.device, dtype=torch.float32)   # noqa: E731
-    scale, shift = f(), f()
-    mean, invstd, ws = (f(), f(), torch.empty(BN_SLICES * C * 3, device=y.device, dtype=torch.float32)) if training else (None, None, None)
-    out = torch.empty_like(y)
+    M, C, out, mean, invstd, scale, shift, ws = _bn_fwd_args("bn_add_relu_fwd", y, gamma, beta, running_mean, running_var, num_batches_tracked, training)
     check(lib().uia_bn_add_relu_fwd(_stream(), _code(y.dtype), int(bool(training)), M, C, _p(y), _p(r), _p(gamma), _p(beta), _p(running_mean),
                                     _p(running_var), _p(num_batches_tracked), float(momentum), float(eps), _p(ws), _p(mean), _p(invstd), _p(scale),
                                     _p(shift), _p(out)), "uia_bn_add_relu_fwd")
@@ -2371,20 +2350,7 @@ def bn_add_relu_fwd(y, r, gamma, beta, running_mean, running_var, num_batches_tr
 
 def bn_add_relu_bwd(y, out, dout, mean, invstd, gamma, want_dr=True):
     """Backward of train-mode bn_add_relu_fwd (uia_bn_add_relu_bwd): returns (dy, dr, dgamma, dbeta); dr is None without want_dr."""
-    _nhwc(y, "bn_add_relu_bwd y")
-    _nhwc(out, "bn_add_relu_bwd out", y.dtype)
-    _nhwc(dout, "bn_add_relu_bwd dout", y.dtype)
-    if dout.shape != y.shape or out.shape != y.shape:
-        raise UiaError("bn_add_relu_bwd: y, out and dout differ in shape")
-    C = y.shape[3]
-    for t, nm in ((mean, "mean"), (invstd, "invstd"), (gamma, "gamma")):
-        if t is None or t.dtype != torch.float32 or not t.is_contiguous() or t.numel() != C:
-            raise UiaError(f"bn_add_relu_bwd: {nm} must be contiguous fp32 [{C}]")
-    M = y.numel() // C
-    ws = torch.empty(BN_SLICES * C * 3, device=y.device, dtype=torch.float32)
-    dgamma = torch.empty(C, device=y.device, dtype=torch.float32)
-    dbeta = torch.empty(C, device=y.device, dtype=torch.float32)
-    dy = torch.empty_like(y)
+    M, C, dy, dgamma, dbeta, ws = _bn_bwd_args("bn_add_relu_bwd", y, ((out, "out"), (dout, "dout")), ((mean, "mean"), (invstd, "invstd"), (gamma, "gamma")))
     dr = torch.empty_like(y) if want_dr else None
     check(lib().uia_bn_add_relu_bwd(_stream(), _code(y.dtype), M, C, _p(y), _p(out), _p(dout), _p(mean), _p(invstd), _p(gamma), _p(ws), _p(dgamma),
                                     _p(dbeta), _p(dy), _p(dr)), "uia_bn_add_relu_bwd")

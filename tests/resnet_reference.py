@@ -325,8 +325,8 @@ CONV_DIRECT_CN = ((3, 2),)
 POOL_HW = ((7, 9), (8, 8), (2, 3))
 POOL_C = (8, 20)
 POOL_DATA = ("random", "equal", "negative", "ties")
-BN_M = (49, 128)                                  # 1·7·7 and 2·8·8
-BN_C = (8, 64, 20)
+BN_M = (49, 128, 257)                             # 1·7·7 and 2·8·8; 257: two slices, the last one shorter
+BN_C = (8, 64, 20, 257)                           # 257: one row lane per channel and a second pass over the channels
 AVG_HW = ((1, 1), (7, 7))
 AVG_C = (8, 20, 512)
 

@@ -373,6 +373,35 @@ def test_bn_add_relu_backward(lib, ops):
     finish(ck)
 
 
+def test_relu_gates_select_and_do_not_multiply(ops):
+    """Where its gate is closed (z <= 0 for bn_relu_bwd, out == 0 for bn_add_relu_bwd) a ReLU backward never reads dout: with +inf there
+    dgamma, dbeta and dy are finite and the bits of the same call with 0 there, and dr is 0.  A gate that multiplied dout by 0 would give NaN."""
+    M, C = 8, 8
+    for dt in DT:
+        y, dout, scale, shift, mean, invstd, gamma = UR.bn_bwd_case(M, C, dt, seed=5)
+        out = torch.relu(UR.rnd(M, C, seed=65)).to(dt)
+        z = torch.addcmul(shift, y.float(), scale)                      # y is clear of the band around z == 0, so fp32 decides as the kernel does
+        v4 = lambda t: up(t).view(1, 1, M, C)                           # noqa: E731
+        bits = lambda t: t.view(torch.int16 if t.dtype == torch.bfloat16 else torch.int32)   # noqa: E731
+        stats = [up(t) for t in (mean, invstd, gamma)]
+        for name, closed in (("bn_relu_bwd", z <= 0), ("bn_add_relu_bwd", out == 0)):
+            assert 0 < int(closed.sum()) < M * C
+            got = []
+            for fill in (float("inf"), 0.0):
+                d = torch.where(closed, torch.full_like(dout, fill), dout)
+                if name == "bn_relu_bwd":
+                    dy, dgamma, dbeta = ops.bn_relu_bwd(v4(y), v4(d), up(scale), up(shift), *stats)
+                    dr = None
+                else:
+                    dy, dr, dgamma, dbeta = ops.bn_add_relu_bwd(v4(y), v4(out), v4(d), *stats)
+                got.append((dy, dgamma, dbeta, dr))
+            for k, a, b in zip(("dy", "dgamma", "dbeta"), got[0], got[1]):
+                assert bool(torch.isfinite(a).all()), f"{name} {dt}: {k} is not finite beside a closed gate"
+                assert torch.equal(bits(a), bits(b)), f"{name} {dt}: {k} depends on dout behind a closed gate"
+            if name == "bn_add_relu_bwd":
+                assert torch.equal(bits(got[0][3]), bits(got[1][3])) and bool((got[0][3].view(M, C)[up(closed)] == 0).all()), f"{name} {dt}: dr behind a closed gate"
+
+
 def test_bn_add_relu_refusals(lib, ops):
     y = torch.zeros(4, 8, dtype=F32, device=dev())
     g = torch.ones(8, dtype=F32, device=dev())
