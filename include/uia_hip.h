@@ -596,6 +596,14 @@ size_t uia_resize_workspace_bytes(int B);
 int uia_resize_batch(void* stream, int B, int C, int S, const uint8_t* src, size_t src_bytes, const int32_t* desc, void* ws, size_t ws_bytes, float* out_images,
                      uint8_t* out_masks);
 
+/* uia_resize_batch for a batch that mixes gray and colour images, three planes out: the reference's contrastive loader (convert("RGB") when the mode
+ * is not RGB, Resize(S, BICUBIC), CenterCrop(S), ToTensor) in one launch.  Word 3 of an image's descriptor is its CHANNEL COUNT, 1 or 3 (there are no
+ * masks): (offset, H, W, channels, dst_h, dst_w, y0, x0).  out_images is fp32 [B,3,S,S]; a one-channel image is resampled once and its result written
+ * to all three planes, which is Pillow's convert("RGB") of an "L" image followed by the resize (the channels run the same arithmetic).  Everything else
+ * — the arithmetic, the limits, the checks made before anything is enqueued with the image's index in uia_last_error(), the workspace
+ * (uia_resize_workspace_bytes(B)), the descriptor's asynchronous copy — is uia_resize_batch's; a channel count other than 1 or 3 is refused. */
+int uia_resize_batch_rgb(void* stream, int B, int S, const uint8_t* src, size_t src_bytes, const int32_t* desc, void* ws, size_t ws_bytes, float* out_images);
+
 /* ---------------------------------------------------------------------------------------------
  * Layout helpers around the GEMMs. */
 int uia_cast(void* stream, int dtype, size_t n, const float* src, void* dst, float scale);          /* dst = T(scale*src) */

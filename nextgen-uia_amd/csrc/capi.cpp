@@ -287,6 +287,9 @@ int uia_resize_batch(void* stream, int B, int C, int S, const uint8_t* src, size
                      uint8_t* out_masks) {
     return uia_resize_batch_launch((hipStream_t)stream, B, C, S, src, src_bytes, desc, ws, ws_bytes, out_images, out_masks);
 }
+int uia_resize_batch_rgb(void* stream, int B, int S, const uint8_t* src, size_t src_bytes, const int32_t* desc, void* ws, size_t ws_bytes, float* out_images) {
+    return uia_resize_batch_rgb_launch((hipStream_t)stream, B, S, src, src_bytes, desc, ws, ws_bytes, out_images);
+}
 
 int uia_im2col_padded(void* stream, int dtype, int B, int C, int H, int W, int P, const float* img, void* cols, int64_t ldo) {
     return uia_im2col_padded_launch((hipStream_t)stream, dtype, B, C, H, W, P, img, cols, (long)ldo);

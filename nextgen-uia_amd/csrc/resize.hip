@@ -7,6 +7,10 @@
 // (y0, x0) of that result is written, planar, as (float)q / 255.0f; its mask (one byte per pixel, H x W) goes through Pillow's nearest scaler and is
 // written as source byte != 0.  An image without a mask in a batch that has some gets a zero mask.
 //
+// uia_resize_batch_rgb is the same tile code for a batch that mixes gray and colour images (the contrastive loader: convert("RGB") when the mode is not
+// RGB, Resize, CenterCrop): word 3 of the descriptor is the image's channel count, 1 or 3, there are no masks, the output has three planes, and a
+// one-channel image is resampled once and written to all three — the channels of Pillow's convert("RGB") of an "L" image run the same arithmetic.
+//
 // Images: Pillow's two-pass 8-bit resample with the bicubic filter (a = -0.5), antialiased: per axis scale = in / dst, filterscale = max(scale, 1),
 // support = 2 filterscale; output xx takes the source pixels xmin .. xmin + xmax - 1 around center = (xx + 0.5) scale with the weights
 // bicubic((x + xmin - center + 0.5) / filterscale), summed in tap order and divided by the sum in float64, rounded to 22-bit fixed point; a pass is
@@ -93,19 +97,18 @@ __device__ void rs_nearest(int n_in, int n_out, int first, int count, int* idx) 
 
 __device__ __forceinline__ int rs_clip8(int ss) { return min(max(ss >> RS_BITS, 0), 255); }
 
-template <int C>
-__global__ __launch_bounds__(RS_THREADS) void resize_kernel(int S, int TR, const uint8_t* __restrict__ src, const int32_t* __restrict__ desc,
-                                                            float* __restrict__ out_images, uint8_t* __restrict__ out_masks) {
+// The tile of one workgroup: C interleaved source channels, written to C planes, or (REPL, C = 1) the one plane written three times.  The LDS
+// tables are the caller's, so that the two instantiations of the mixed kernel share them.
+template <int C, bool REPL>
+__device__ __forceinline__ void rs_tile(int S, int TR, const uint8_t* __restrict__ src, int off, int H, int W, int moff, int dst_h, int dst_w, int wy, int wx,
+                                        float* __restrict__ out_images, uint8_t* __restrict__ out_masks, int (*hk)[RS_KMAX], int (*vk)[RS_KMAX], int* hmin,
+                                        int* hcnt, int* vmin, int* vcnt, int* nx, int* ny, uint8_t* mid) {
     constexpr int PITCH = RS_TC * C;               // bytes of an intermediate row
     constexpr int ROWS_CAP = RS_MID_BYTES / PITCH;
-    __shared__ int hk[RS_TC][RS_KMAX], vk[RS_TR_MAX][RS_KMAX];
-    __shared__ int hmin[RS_TC], hcnt[RS_TC], vmin[RS_TR_MAX], vcnt[RS_TR_MAX], nx[RS_TC], ny[RS_TR_MAX];
-    __shared__ uint8_t mid[RS_MID_BYTES];
+    constexpr int OC = REPL ? 3 : C;               // planes of an output image
 
     const int tid = threadIdx.x;
     const size_t b = blockIdx.z;
-    const int32_t* d = desc + b * RS_DESC;
-    const int off = d[0], H = d[1], W = d[2], moff = d[3], dst_h = d[4], dst_w = d[5], wy = d[6], wx = d[7];
     const int row0 = blockIdx.y * TR, col0 = blockIdx.x * RS_TC;                 // of the window
     const int TRh = min(min(TR, RS_TR_MAX), S - row0), TCw = min(RS_TC, S - col0);
     if (TRh <= 0 || TCw <= 0) return;
@@ -142,7 +145,13 @@ __global__ __launch_bounds__(RS_THREADS) void resize_kernel(int S, int TR, const
         const uint8_t* p = mid + first * PITCH + x * C + c;
         int ss = 1 << (RS_BITS - 1);
         for (int k = 0; k < n; ++k) ss += (int)p[k * PITCH] * vk[y][k];
-        out_images[((b * C + c) * S + (size_t)(row0 + y)) * S + col0 + x] = (float)rs_clip8(ss) / 255.0f;
+        const float v = (float)rs_clip8(ss) / 255.0f;
+        float* o = out_images + ((b * OC + c) * S + (size_t)(row0 + y)) * S + col0 + x;
+        o[0] = v;
+        if (REPL) {                                                              // a gray image in a three-plane batch: convert("RGB") of "L" repeats the byte
+            o[(size_t)S * S] = v;
+            o[2 * (size_t)S * S] = v;
+        }
     }
 
     if (out_masks != nullptr) {
@@ -153,6 +162,30 @@ __global__ __launch_bounds__(RS_THREADS) void resize_kernel(int S, int TR, const
             out_masks[(b * S + (size_t)(row0 + y)) * S + col0 + x] = v;
         }
     }
+}
+
+#define RS_TILE_LDS                                                                                                     \
+    __shared__ int hk[RS_TC][RS_KMAX], vk[RS_TR_MAX][RS_KMAX];                                                          \
+    __shared__ int hmin[RS_TC], hcnt[RS_TC], vmin[RS_TR_MAX], vcnt[RS_TR_MAX], nx[RS_TC], ny[RS_TR_MAX];                \
+    __shared__ uint8_t mid[RS_MID_BYTES]
+
+template <int C>
+__global__ __launch_bounds__(RS_THREADS) void resize_kernel(int S, int TR, const uint8_t* __restrict__ src, const int32_t* __restrict__ desc,
+                                                            float* __restrict__ out_images, uint8_t* __restrict__ out_masks) {
+    RS_TILE_LDS;
+    const int32_t* d = desc + (size_t)blockIdx.z * RS_DESC;
+    rs_tile<C, false>(S, TR, src, d[0], d[1], d[2], d[3], d[4], d[5], d[6], d[7], out_images, out_masks, hk, vk, hmin, hcnt, vmin, vcnt, nx, ny, mid);
+}
+
+// uia_resize_batch_rgb: word 3 of the descriptor is the image's channel count; blockIdx.z is the image, so the branch is uniform over the workgroup
+__global__ __launch_bounds__(RS_THREADS) void resize_rgb_kernel(int S, int TR, const uint8_t* __restrict__ src, const int32_t* __restrict__ desc,
+                                                                float* __restrict__ out_images) {
+    RS_TILE_LDS;
+    const int32_t* d = desc + (size_t)blockIdx.z * RS_DESC;
+    if (d[3] == 1)
+        rs_tile<1, true>(S, TR, src, d[0], d[1], d[2], -1, d[4], d[5], d[6], d[7], out_images, nullptr, hk, vk, hmin, hcnt, vmin, vcnt, nx, ny, mid);
+    else
+        rs_tile<3, false>(S, TR, src, d[0], d[1], d[2], -1, d[4], d[5], d[6], d[7], out_images, nullptr, hk, vk, hmin, hcnt, vmin, vcnt, nx, ny, mid);
 }
 
 int rs_ksize(int n_in, int n_out) {
@@ -167,9 +200,10 @@ size_t uia_resize_ws_bytes(int B) {
     return ((size_t)B * RS_DESC * sizeof(int32_t) + 255) & ~(size_t)255;
 }
 
-int uia_resize_batch_launch(hipStream_t stream, int B, int C, int S, const uint8_t* src, size_t src_bytes, const int32_t* desc, void* ws, size_t ws_bytes,
-                            float* out_images, uint8_t* out_masks) {
-    const char* who = "uia_resize_batch";
+// Both entries.  uia_resize_batch: C channels in and out, word 3 of an image is its mask offset.  uia_resize_batch_rgb (mixed): word 3 is the image's
+// channel count, three planes out, no masks.
+static int rs_launch(const char* who, bool mixed, hipStream_t stream, int B, int C, int S, const uint8_t* src, size_t src_bytes, const int32_t* desc, void* ws,
+                     size_t ws_bytes, float* out_images, uint8_t* out_masks) {
     UIA_CHECK_ARG(B >= 1 && B <= RS_MAX_B && S >= RS_MIN_S && S <= RS_MAX_S, "%s: bad shape B=%d S=%d (1 <= B <= %d, %d <= S <= %d)", who, B, S, RS_MAX_B,
                   RS_MIN_S, RS_MAX_S);
     UIA_CHECK_ARG(C == 1 || C == 3, "%s: C=%d channels (1 or 3)", who, C);
@@ -182,14 +216,15 @@ int uia_resize_batch_launch(hipStream_t stream, int B, int C, int S, const uint8
     UIA_CHECK_ARG(!overlap(src, src_bytes, out_images, (size_t)B * C * pix * sizeof(float)) && (!out_masks || !overlap(src, src_bytes, out_masks, (size_t)B * pix)) &&
                       (!out_masks || !overlap(out_images, (size_t)B * C * pix * sizeof(float), out_masks, (size_t)B * pix)),
                   "%s: the outputs must not be the inputs or each other (the ranges overlap)", who);
-    const int rows_cap = RS_MID_BYTES / (RS_TC * C);
     int TR = RS_TR_MAX;
     for (int b = 0; b < B; ++b) {                                  // every image is checked before anything is enqueued
         const int32_t* d = desc + (size_t)b * RS_DESC;
-        const long long off = d[0], H = d[1], W = d[2], moff = d[3], dst_h = d[4], dst_w = d[5], y0 = d[6], x0 = d[7];
+        const long long off = d[0], H = d[1], W = d[2], moff = mixed ? -1 : d[3], dst_h = d[4], dst_w = d[5], y0 = d[6], x0 = d[7];
+        const int Cb = mixed ? d[3] : C;
+        UIA_CHECK_ARG(Cb == 1 || Cb == 3, "%s: image %d has %d channels (1 or 3)", who, b, Cb);
         UIA_CHECK_ARG(H >= 1 && W >= 1, "%s: image %d is %lld x %lld (H, W >= 1)", who, b, H, W);
-        UIA_CHECK_ARG(off >= 0 && (unsigned long long)off + (unsigned long long)H * W * C <= src_bytes,
-                      "%s: image %d (offset %lld, %lld x %lld x %d) leaves the source buffer of %zu bytes", who, b, off, H, W, C, src_bytes);
+        UIA_CHECK_ARG(off >= 0 && (unsigned long long)off + (unsigned long long)H * W * Cb <= src_bytes,
+                      "%s: image %d (offset %lld, %lld x %lld x %d) leaves the source buffer of %zu bytes", who, b, off, H, W, Cb, src_bytes);
         UIA_CHECK_ARG(moff >= -1, "%s: image %d has mask offset %lld (an offset, or -1 for none)", who, b, moff);
         if (moff >= 0) {
             UIA_CHECK_ARG(out_masks != nullptr, "%s: image %d has a mask but out_masks is null", who, b);
@@ -203,7 +238,8 @@ int uia_resize_batch_launch(hipStream_t stream, int B, int C, int S, const uint8
         const int kh = rs_ksize((int)W, (int)dst_w), kv = rs_ksize((int)H, (int)dst_h);
         UIA_CHECK_ARG(kh <= RS_KMAX && kv <= RS_KMAX, "%s: image %d: %lld x %lld -> %lld x %lld needs %d taps per pixel (at most %d: a downscale of at most 32x)", who,
                       b, H, W, dst_h, dst_w, kh > kv ? kh : kv, RS_KMAX);
-        if (H != dst_h) {                                          // rows of a tile: (TR - 1) scale + ksize source rows must fit the intermediate
+        if (H != dst_h) {                                          // rows of a tile: (TR - 1) scale + ksize source rows must fit this image's intermediate
+            const int rows_cap = RS_MID_BYTES / (RS_TC * Cb);
             const double scale = (double)H / (double)dst_h;
             const double fit = floor((double)(rows_cap - kv - 1) / scale) + 1.0;
             if (fit < (double)TR) TR = fit < 1.0 ? 1 : (int)fit;
@@ -211,10 +247,23 @@ int uia_resize_batch_launch(hipStream_t stream, int B, int C, int S, const uint8
     }
     UIA_CHECK_HIP(hipMemcpyAsync(ws, desc, (size_t)B * RS_DESC * sizeof(int32_t), hipMemcpyHostToDevice, stream));
     const dim3 grid((unsigned)((S + RS_TC - 1) / RS_TC), (unsigned)((S + TR - 1) / TR), (unsigned)B);
-    if (C == 1)
+    if (mixed)
+        resize_rgb_kernel<<<grid, dim3(RS_THREADS), 0, stream>>>(S, TR, src, (const int32_t*)ws, out_images);
+    else if (C == 1)
         resize_kernel<1><<<grid, dim3(RS_THREADS), 0, stream>>>(S, TR, src, (const int32_t*)ws, out_images, out_masks);
     else
         resize_kernel<3><<<grid, dim3(RS_THREADS), 0, stream>>>(S, TR, src, (const int32_t*)ws, out_images, out_masks);
     UIA_CHECK_LAUNCH();
     return 0;
 }
+
+int uia_resize_batch_launch(hipStream_t stream, int B, int C, int S, const uint8_t* src, size_t src_bytes, const int32_t* desc, void* ws, size_t ws_bytes,
+                            float* out_images, uint8_t* out_masks) {
+    return rs_launch("uia_resize_batch", false, stream, B, C, S, src, src_bytes, desc, ws, ws_bytes, out_images, out_masks);
+}
+
+int uia_resize_batch_rgb_launch(hipStream_t stream, int B, int S, const uint8_t* src, size_t src_bytes, const int32_t* desc, void* ws, size_t ws_bytes,
+                                float* out_images) {
+    return rs_launch("uia_resize_batch_rgb", true, stream, B, 3, S, src, src_bytes, desc, ws, ws_bytes, out_images, nullptr);
+}
+

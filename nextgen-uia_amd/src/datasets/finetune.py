@@ -4,7 +4,8 @@ The reference reads CSV-listed image/caption pairs from hard-coded roots with PI
 is outside the hot path and whose dependencies are absent from the build image.  What the hot path needs from it is the
 batch contract: images float32 [B,3,S,S] in [0,1] WITHOUT mean/std normalisation (:17-24) and a list of caption strings,
 `drop_last=True`.  `--synthetic` provides exactly that deterministically; real data can be supplied as a .pt file of
-{"images": uint8/float [N,3,S,S], "texts": [str]*N} via --data_pt.
+{"images": uint8/float [N,3,S,S], "texts": [str]*N} via --data_pt.  The reference's CSV folders themselves are read by
+src/datasets/captions.py (--finetune_root), with Pillow in the workers and the resize on the device.
 """
 import os
 
@@ -199,8 +200,8 @@ class DataModule:
             self.train = SyntheticPairs(args.synthetic_train, args.img_size, args.seed)
             self.val = SyntheticPairs(args.synthetic_val, args.img_size, args.seed + 1)
         else:
-            raise RuntimeError("no dataset: pass --synthetic or --data_pt (the reference's CSV/PIL loaders need torchvision, "
-                               "which is outside this build)")
+            raise RuntimeError("no dataset: pass --synthetic, --data_pt or --finetune_root (the reference's caption folders, read by "
+                               "src/datasets/captions.py)")
         self.train_sampler = self.val_sampler = None
 
     MAX_WORKERS = 6         # loader processes per rank (the reference's --num_workers default is 8; a one-GPU job's CPU share on the MI355X boxes is 16)

@@ -31,7 +31,8 @@ DESC = 8                                                        # int32 per imag
 MAX_WORKERS = 16
 MIN_SIZE, MAX_SIZE = 8, 1024                                    # img_size the kernel takes
 OUT_OF_SCOPE = ("--data_root reads the reference's dataset folders for the supervised classification and segmentation entries only; {what} takes "
-                "--synthetic or --data_pt (DESIGN.md, \"Not built\")")
+                "--synthetic or --data_pt (DESIGN.md, \"Not built\"){hint}")
+CAPTION_HINT = "; the caption folders of the contrastive fine-tune are read with --finetune_root"
 
 
 def _pil():
@@ -51,7 +52,7 @@ def chosen(args):
 def refuse(args, what):
     """Entry points outside this loader's scope call this before anything else."""
     if getattr(args, "data_root", None):
-        raise RuntimeError(OUT_OF_SCOPE.format(what=what))
+        raise RuntimeError(OUT_OF_SCOPE.format(what=what, hint=CAPTION_HINT if "contrastive" in what else ""))
 
 
 def pack_ragged(items):

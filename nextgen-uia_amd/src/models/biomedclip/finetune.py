@@ -3,7 +3,7 @@
 Same command line (every flag and default of reference :32-111), same loop semantics (:211-361): micro-batch InfoNCE,
 (loss / accumulation_steps).backward(), non-finite batches skipped, clip_grad_norm_ → AdamW → cosine LR once per cycle,
 validation each epoch, best-val checkpoint of the adapter parameters only (names containing "mona"/"lora", :200-208),
-early stopping, runs/<exp>/{log.log,best_model.pth}.  Added, non-breaking: --dtype {bf16,fp32}, --synthetic / --data_pt,
+early stopping, runs/<exp>/{log.log,best_model.pth}.  Added, non-breaking: --dtype {bf16,fp32}, --synthetic / --data_pt / --finetune_root (the reference's caption folders as released), --tokenizer_json (real token ids),
 --ckpt_path (an open_clip BiomedCLIP state dict; without it the towers are randomly initialised because the build image
 has no network), and data parallelism when launched under torch.distributed.run (one process per GPU, one RCCL
 all-reduce of the flat adapter-gradient buffer per optimiser update ≡ the reference's accumulation).
@@ -26,6 +26,7 @@ import torch
 from src.adapters import inject_lora_to_biomedclip, inject_mona_variant_to_open_clip
 from src.models import contrastive
 from src.third_party.biomedclip.model import SyntheticTokenizer, create_biomedclip
+from src.utils import tokenizer_file
 from src.utils.tools import default_device, parse_config
 
 
@@ -69,8 +70,9 @@ def get_args(argv=None):
 
 
 def make_tokenizer(args):
-    cfg = parse_config(args.model_config) if args.model_config else None
-    return SyntheticTokenizer(256 if cfg is None else cfg["text_cfg"]["max_position_embeddings"])
+    tc = {} if not args.model_config else parse_config(args.model_config)["text_cfg"]
+    context = tc.get("max_position_embeddings", 256)
+    return tokenizer_file.from_args(args, context, tc.get("vocab_size", 30522), pools_at_argmax=False) or SyntheticTokenizer(context)
 
 
 def prepare_model(args):

@@ -8,7 +8,7 @@ src/third_party/openai_clip/model.py (sequence-first blocks, nn.MultiheadAttenti
 
 Differences forced by the build image: `clip.load` (torchvision transforms, the BPE vocabulary file) is not available — --ckpt is read as an OpenAI TorchScript archive or a
 plain state dict when the file exists, otherwise the ViT-B/16 geometry is randomly initialised; captions are tokenised by the deterministic stand-in tokenizer (context 77,
-<start>/<end> ids of the CLIP vocabulary).  Added, non-breaking: --dtype, --synthetic / --data_pt, --model_config, data parallelism under torch.distributed.run, and --zero_shot_eval (the reference's
+<start>/<end> ids of the CLIP vocabulary).  Added, non-breaking: --dtype, --synthetic / --data_pt / --finetune_root (the reference's caption folders as released), --tokenizer_json (real token ids), --model_config, data parallelism under torch.distributed.run, and --zero_shot_eval (the reference's
 run_zero_shot_evaluation, :239, opt-in here: src/models/clip/zero_shot.py once per dataset, each a fresh child process)."""
 import argparse
 import dataclasses
@@ -21,6 +21,7 @@ from src.adapters import inject_mona_variant_to_clip
 from src.models import contrastive
 from src.third_party.open_clip.model import SyntheticClipTokenizer
 from src.third_party.openai_clip.model import load_clip
+from src.utils import tokenizer_file
 from src.utils.tools import default_device, parse_config
 
 
@@ -59,7 +60,7 @@ def _geometry(args):
 
 def make_tokenizer(args):
     geo = _geometry(args)
-    return SyntheticClipTokenizer(geo[5], geo[6])
+    return tokenizer_file.from_args(args, geo[5], geo[6], pools_at_argmax=True) or SyntheticClipTokenizer(geo[5], geo[6])
 
 
 def prepare_model(args):

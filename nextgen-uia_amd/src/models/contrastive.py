@@ -10,6 +10,10 @@ accumulate) and every accumulation boundary through the device-guarded clip + Ad
 non-finite skip is decided on the device, the epoch's loss sum / counts / skipped indices come back in ONE read at the end of the epoch, validation reads once per
 pass, batches arrive through a double-buffered prefetcher.  Data parallel under torch.distributed.run: one process per GPU, rank 0 saves.
 
+Data: --data_pt, then --synthetic (src/datasets/finetune.py), then --finetune_root, the reference's caption folders as released (src/datasets/captions.py: workers
+decode into a ring of byte slots, `RgbResizeStage` behind the prefetcher's event makes the [B, 3, S, S] batch in one uia_resize_batch_rgb launch); --data_root is
+refused.  --tokenizer_json puts a tokenizer file's ids in the stand-in tokenizer's place (src/utils/tokenizer_file.py, through each family's `make_tokenizer`).
+
 What differs by family and cannot be read from `args` is a field of `Recipe`; what can is read from `args` (--accumulation_steps, default 1; --grad_clip, default 1.0;
 --method, default "mona": what the checkpoint holds).  What differs by model is an argument: `prepare_model(args) -> (model, tokenizer)` and `make_tokenizer(args)`.
 """
@@ -26,6 +30,7 @@ from dataclasses import dataclass
 import numpy as np
 import torch
 
+from src.datasets import captions
 from src.datasets import finetune as dataset_finetune
 from src.losses import InfoNCELoss
 from src.utils.tools import model_summary, setup_logging
@@ -93,6 +98,9 @@ def add_build_args(p):
     p.add_argument("--synthetic_val", type=int, default=128)
     p.add_argument("--data_pt", type=str, default=None, help=".pt with {'images': [N,3,S,S], 'texts': [str]}")
     p.add_argument("--data_root", type=str, default=None, help="refused here: the folder loader serves the supervised classification / segmentation entries")
+    p.add_argument("--finetune_root", type=str, default=None, help="the reference's caption folders as released: DIR/{medpix_dataset,pmc_curd_dataset}/{<name>.csv,images/} "
+                   "(taken after --data_pt and --synthetic)")
+    p.add_argument("--tokenizer_json", type=str, default=None, help="a tokenizer file of the `tokenizers` library: real token ids in place of the stand-in tokenizer")
     p.add_argument("--model_config", type=str, default=None, help="python literal overriding the model geometry, in the form the family's model constructor takes (tests)")
 
 
@@ -114,7 +122,10 @@ def train(args, recipe, prepare_model, make_tokenizer):
     rank, _, world = dist_env()
     if not torch.cuda.is_initialized():                         # a fresh CLI process (not a caller that is already running other GPU / CPU work in this process)
         torch.set_num_threads(max(1, min(4, torch.get_num_threads())))      # host tensor work here is one staging copy per batch; the default (every logical CPU of the node) oversubscribes a job's CPU share
-    dm = dataset_finetune.DataModule(args, rank=rank, world=world, tokenizer=make_tokenizer(args))
+    folders = captions.chosen(args)                             # --finetune_root: workers decode, the batch is made on the device (src/datasets/captions.py)
+    if folders and not getattr(args, "tokenizer_json", None):
+        logging.warning("--finetune_root without --tokenizer_json: the captions go through the stand-in tokenizer, whose ids mean nothing to a pretrained text tower")
+    dm = (captions if folders else dataset_finetune).DataModule(args, rank=rank, world=world, tokenizer=make_tokenizer(args))
     trainloader, valloader = dm.train_dataloader(), dm.val_dataloader()
     dm.start_workers()                                         # loader worker processes are forked BEFORE this process touches the GPU
     bind_device(args)                                          # data parallel: cuda:LOCAL_RANK before anything is allocated
@@ -135,8 +146,11 @@ def train(args, recipe, prepare_model, make_tokenizer):
     loop = ContrastiveLoop(model, criterion, opt, accumulation_steps=accumulation_steps, lr=args.lr, lr_min=args.lr_min, total_updates=updates_per_epoch * args.epochs,
                            features=recipe.features, discard_on_skip=recipe.discard_on_skip)
     features = recipe.features or (lambda fi, ft: (fi, ft))
-    train_pf = DevicePrefetcher(trainloader, tokenizer, args.device)
-    val_pf = DevicePrefetcher(valloader, tokenizer, args.device)
+    if folders:
+        train_pf, val_pf = captions.CaptionPrefetcher(trainloader, args.device), captions.CaptionPrefetcher(valloader, args.device)
+        stage = captions.RgbResizeStage(args.img_size)
+    else:
+        train_pf, val_pf, stage = DevicePrefetcher(trainloader, tokenizer, args.device), DevicePrefetcher(valloader, tokenizer, args.device), None
 
     best_loss, best_epoch, patience = float("inf"), 0, 0
     avg_train, update_count, epoch_ms = 0.0, 0, []
@@ -149,6 +163,9 @@ def train(args, recipe, prepare_model, make_tokenizer):
         t0, w0, enq, gw0 = time.perf_counter(), train_pf.wait_s, 0.0, getattr(opt, "gpu_wait_s", 0.0) + UF._STATE.get("gpu_wait_s", 0.0)
         for batch_idx, (images, tokens, ready) in enumerate(batches):
             t1 = time.perf_counter()
+            if stage is not None:                                # the ragged batch -> [B, 3, S, S]: one launch behind the prefetcher's event
+                torch.cuda.current_stream().wait_event(ready)
+                images = stage(images)
             loop.micro(images, tokens, batch_idx, ready=ready)
             enq += time.perf_counter() - t1
         t2 = time.perf_counter()
@@ -167,6 +184,8 @@ def train(args, recipe, prepare_model, make_tokenizer):
         with torch.no_grad():
             for images, tokens, ready in val_pf:
                 torch.cuda.current_stream().wait_event(ready)
+                if stage is not None:
+                    images = stage(images)
                 loss = criterion(*features(model.encode_image(images), model.encode_text(tokens)))
                 ok = torch.isfinite(loss)
                 vstat += torch.stack([torch.where(ok, loss, torch.zeros_like(loss)), ok.to(loss.dtype)])

@@ -5,7 +5,7 @@ Same command line (every flag and default of reference :26-64; default --mona_va
 accumulation) and loop semantics (:92-218): per batch InfoNCE on L2-normalised features, non-finite batches skipped,
 clip_grad_norm_(1.0) → AdamW → cosine LR every iteration, a validation pass per epoch in eval mode, best-val checkpoint of
 the parameters whose name contains "mona", early stopping by --patience, runs/<exp>/{log.log,best_model.pth}.
-Added, non-breaking: --dtype, --synthetic / --data_pt, --ckpt_path, --model_config, data parallelism under
+Added, non-breaking: --dtype, --synthetic / --data_pt / --finetune_root (the reference's caption folders as released), --tokenizer_json (real token ids), --ckpt_path, --model_config, data parallelism under
 torch.distributed.run, and --zero_shot_eval: the reference's post-training zero-shot evaluation (run_zero_shot_evaluation, :240-296), which the
 reference always runs, is opt-in here — rank 0 starts src/models/metaclip/zero_shot.py once per dataset, each a fresh child process.
 The loop is src/models/contrastive.py with its CLIP_FAMILY recipe; this module keeps the flags and the model.
@@ -22,6 +22,7 @@ import torch
 from src.adapters import inject_mona_variant_to_open_clip
 from src.models import contrastive
 from src.third_party.open_clip.model import SyntheticClipTokenizer, create_metaclip
+from src.utils import tokenizer_file
 from src.utils.tools import default_device, parse_config
 
 
@@ -57,7 +58,8 @@ def get_args(argv=None):
 
 def make_tokenizer(args):
     tc = ((parse_config(args.model_config) if args.model_config else None) or {}).get("text_cfg", {})
-    return SyntheticClipTokenizer(tc.get("context_length", 77), tc.get("vocab_size", 49408))
+    context, vocab = tc.get("context_length", 77), tc.get("vocab_size", 49408)
+    return tokenizer_file.from_args(args, context, vocab, pools_at_argmax=True) or SyntheticClipTokenizer(context, vocab)
 
 
 def prepare_model(args):

@@ -10,7 +10,7 @@ measured step) with this family's model preparation (:66-108):
   * every parameter frozen, the adapters injected, parameters whose lower-cased name contains "mona" trainable, fp32 masters (:89-106).
 Differences forced by the build image: open_clip's HFTokenizer("microsoft/BiomedNLP-BiomedBERT-base-uncased-abstract", context_length=77) needs the network — captions are
 tokenised by the deterministic BERT-style stand-in (CLS 2, SEP 3, ids 1000-30000, pad 0; context 77); without a checkpoint file the tower is randomly initialised.
-Added, non-breaking: --dtype, --synthetic / --data_pt, --model_config, data parallelism under torch.distributed.run, and --zero_shot_eval (the reference's
+Added, non-breaking: --dtype, --synthetic / --data_pt / --finetune_root (the reference's caption folders as released), --tokenizer_json (real token ids), --model_config, data parallelism under torch.distributed.run, and --zero_shot_eval (the reference's
 run_zero_shot_evaluation, opt-in here: src/models/unimedclip/zero_shot.py once per dataset, each a fresh child process, on the --version / --ckpt trained on)."""
 import argparse
 import dataclasses
@@ -27,6 +27,7 @@ from src.adapters import inject_mona_variant_to_open_clip
 from src.models import contrastive
 from src.third_party.biomedclip.model import SyntheticTokenizer
 from src.third_party.open_clip.model import create_native_clip
+from src.utils import tokenizer_file
 from src.utils.tools import default_device, parse_config
 
 
@@ -66,7 +67,9 @@ def _config(args):
 
 def make_tokenizer(args):
     cfg = _config(args) or {}
-    return SyntheticTokenizer(cfg.get("context_length", 77))
+    context = cfg.get("context_length", 77)
+    # the native open_clip text tower pools at the arg-max id like the other CLIP layouts: a BERT vocabulary, whose [SEP] is a small id, is refused
+    return tokenizer_file.from_args(args, context, cfg.get("vocab_size", 49408), pools_at_argmax=True) or SyntheticTokenizer(context)
 
 
 def prepare_model(args):

@@ -1994,6 +1994,27 @@ def resize_batch(src, desc, S, C=1, out_images=None, out_masks=None, ws=None):
     return out_images, out_masks
 
 
+def resize_batch_rgb(src, desc, S, out_images=None, ws=None):
+    """resize_batch for a batch that mixes gray and colour images: word 3 of an image's descriptor is its channel count, 1 or 3, (offset, H, W, channels,
+    dst_h, dst_w, y0, x0) -> out_images fp32 [B, 3, S, S]; a one-channel image is resampled once and written to all three planes (PIL's convert("RGB") of
+    an "L" image, then the resize).  No masks.  Enqueued only; out_images and ws may be handed in to be reused."""
+    _p(src)
+    if src.dim() != 1 or src.dtype != torch.uint8 or not src.is_contiguous():
+        raise UiaError(f"resize_batch_rgb: src must be a contiguous 1-D uint8 tensor, got {src.dtype} {tuple(src.shape)}")
+    if (not isinstance(desc, torch.Tensor) or desc.is_cuda or desc.dtype != torch.int32 or desc.dim() != 2 or desc.shape[1] != RESIZE_DESC
+            or desc.shape[0] < 1 or not desc.is_contiguous()):
+        raise UiaError(f"resize_batch_rgb: desc must be a contiguous host int32 tensor [B, {RESIZE_DESC}]")
+    B, S = desc.shape[0], int(S)
+    if out_images is None:
+        out_images = torch.empty((B, 3, S, S), dtype=torch.float32, device=src.device)
+    if tuple(out_images.shape) != (B, 3, S, S) or out_images.dtype != torch.float32 or not out_images.is_contiguous() or out_images.device != src.device:
+        raise UiaError(f"resize_batch_rgb: out_images must be contiguous {torch.float32} [{B}, 3, {S}, {S}] on the source's device")
+    if ws is None:
+        ws = resize_workspace(B, src.device)
+    check(lib().uia_resize_batch_rgb(_stream(), B, S, _p(src), src.numel(), desc.data_ptr(), _p(ws), ws.numel(), _p(out_images)), "uia_resize_batch_rgb")
+    return out_images
+
+
 # ---------------------------------------------------------------- DINOv2 UNet decoder (csrc/unet_conv.hip, unet_bn.hip, unet_resample.hip)
 CONV3, CONVT_FWD, CONVT_BWD, CONV1 = 0, 1, 2, 3      # uia_conv_igemm / uia_conv_wgrad modes
 BN_SLICES = 256                            # UIA_BN_SLICES
