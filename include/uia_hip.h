@@ -604,6 +604,33 @@ int uia_resize_batch(void* stream, int B, int C, int S, const uint8_t* src, size
  * (uia_resize_workspace_bytes(B)), the descriptor's asynchronous copy — is uia_resize_batch's; a channel count other than 1 or 3 is refused. */
 int uia_resize_batch_rgb(void* stream, int B, int S, const uint8_t* src, size_t src_bytes, const int32_t* desc, void* ws, size_t ws_bytes, float* out_images);
 
+/* The way back from a model's S x S logits to each image's own H x W: the inverse of uia_resize_batch's square squash, one launch per batch
+ * (csrc/seg_native.hip).  logits fp32 [B,2,S,S], contiguous, 4-byte aligned.  src: the batch's ragged DEVICE byte buffer of src_bytes bytes (< 2^31) as
+ * uia_resize_batch read it, gray bytes H_b x W_b back to back; NULL (src_bytes ignored) when no image asks for an overlay.  out: one DEVICE byte buffer
+ * of out_bytes bytes (< 2^31).  desc: a HOST array int32 [B][8], per image (src_offset or -1, H, W, mask_out_offset, overlay_out_offset or -1, 0, 0, 0).
+ * stats: DEVICE int32 [B][8].  Offsets are arbitrary bytes: no alignment is asked of src or out (4-byte stores are used where an address allows them,
+ * decided inside the kernel).
+ * For native pixel (y, x) of image b the two logit planes are sampled as torch.nn.functional.interpolate(size=(H, W), mode="bilinear",
+ * align_corners=False) samples them, in fp32, every product and sum rounded once: scale_y = (float)S / H, sy = max(scale_y * (y + 0.5f) - 0.5f, 0),
+ * y0 = (int)sy, y1 = min(y0 + 1, S - 1), ly = sy - y0, the same for x; per plane c the taps are combined rows first, then columns:
+ * v_c[k] = (1 - ly) L_c[y0][k] + ly L_c[y1][k] for k = x0, x1, then u_c = (1 - lx) v_c[x0] + lx v_c[x1]; a tap whose weight is exactly 0 does not enter
+ * (ly == 0: v_c[k] = L_c[y0][k]; lx == 0: u_c = v_c[x0]), so H = W = S gives the logits themselves.
+ * p = 255 where argmax over (u_0, u_1) is class 1 by torch's rules (a tie, -0.0 against +0.0 included, goes to class 0; NaN is the maximum; NaN in
+ * both goes to class 0), the prediction uia_seg_viz, uia_surface_distances and the Dice / IoU metrics use, else 0.
+ * Outputs: the mask, H * W bytes of p at out + mask_out_offset, plain row-major; when src_offset and overlay_out_offset are both >= 0 the overlay,
+ * H * W * 3 bytes (g, max(g, p), g) at out + overlay_out_offset with g the source byte at src_offset + y * W + x (uia_seg_viz's overlay without a ground
+ * truth); stats[b] = (foreground pixel count, ymin, xmin, ymax, xmax, 0, 0, 0), (0, INT_MAX, INT_MAX, -1, -1, 0, 0, 0) for an empty mask: the call sets
+ * that initial value itself on `stream`.  Every byte of the ranges and of stats is written, nothing beside them.
+ * Checked before anything is enqueued (non-zero, nothing written, the image's index in uia_last_error()): 1 <= B <= 65535, 8 <= S <= 1024,
+ * 1 <= H, W <= 16384, null logits / desc / out / ws / stats, a null src when an image asks for an overlay, offsets below -1, a source image, mask or
+ * overlay that leaves its buffer, output ranges that overlap each other, src, logits, stats or the workspace, a non-zero reserved descriptor word.
+ * The descriptor is then copied to the workspace with hipMemcpyAsync on `stream`, so a pinned descriptor must stay as it is until that copy has run.
+ * Asynchronous, deterministic (integer atomics only).  ws: uia_seg_native_workspace_bytes(B) of 4-byte aligned scratch (0 for a B outside the
+ * limits): the device copy of the descriptor. */
+size_t uia_seg_native_workspace_bytes(int B);
+int uia_seg_predict_native(void* stream, int B, int S, const float* logits, const uint8_t* src, size_t src_bytes, const int32_t* desc, uint8_t* out,
+                           size_t out_bytes, void* ws, size_t ws_bytes, int32_t* stats);
+
 /* ---------------------------------------------------------------------------------------------
  * Layout helpers around the GEMMs. */
 int uia_cast(void* stream, int dtype, size_t n, const float* src, void* dst, float scale);          /* dst = T(scale*src) */

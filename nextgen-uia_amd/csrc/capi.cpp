@@ -291,6 +291,12 @@ int uia_resize_batch_rgb(void* stream, int B, int S, const uint8_t* src, size_t 
     return uia_resize_batch_rgb_launch((hipStream_t)stream, B, S, src, src_bytes, desc, ws, ws_bytes, out_images);
 }
 
+size_t uia_seg_native_workspace_bytes(int B) { return uia_seg_native_ws_bytes(B); }
+int uia_seg_predict_native(void* stream, int B, int S, const float* logits, const uint8_t* src, size_t src_bytes, const int32_t* desc, uint8_t* out,
+                           size_t out_bytes, void* ws, size_t ws_bytes, int32_t* stats) {
+    return uia_seg_predict_native_launch((hipStream_t)stream, B, S, logits, src, src_bytes, desc, out, out_bytes, ws, ws_bytes, stats);
+}
+
 int uia_im2col_padded(void* stream, int dtype, int B, int C, int H, int W, int P, const float* img, void* cols, int64_t ldo) {
     return uia_im2col_padded_launch((hipStream_t)stream, dtype, B, C, H, W, P, img, cols, (long)ldo);
 }

@@ -1,0 +1,177 @@
+"""Prediction on pictures without labels: a trained supervised entry applied to a directory of images, at each image's own size.
+
+    python -m src.models.predict --entry biomedclip.segmentation --images DIR --out DIR [--checkpoint FILE] [--no-overlay] -- <that entry's own flags>
+
+--entry names a module src.models.<family>.<segmentation|classification> (ENTRIES below: the supervised entries, CLIPSeg with its per-batch prompt);
+everything else — the few-shot, fine-tune, zero-shot and retrieval modules, a module that does not exist — is refused by name before a model is built.
+Everything after `--` goes to the entry's own get_args; the model is its prepare_model(args); the checkpoint defaults to
+runs/<exp>/<dataset>/train/best_model.pth, the file the entry's test() loads, and is loaded the same way (model.load_checkpoint, UF.WEIGHTS.bump(),
+eval(), no_grad).  A missing image directory or checkpoint and an OUT that is not empty are refused before the GPU is initialised.
+
+Segmentation, per batch: folder.RaggedPrefetcher -> folder.ResizeStage (PIL's resize on the device) -> the task's to_input -> the model -> ONE launch of
+uia_hip.ops.seg_predict_native on the batch's own ragged bytes (the S x S logits upsampled to every image's H x W, arg-max, mask, overlay, statistics) ->
+one pinned copy back -> at most four writer threads (src/utils/viz.NativeMaskWriter):
+    OUT/masks/<stem>.png       8-bit grey, the image's own size        OUT/overlays/<stem>.png    RGB, unless --no-overlay
+    OUT/predictions.csv        name,width,height,foreground_pixels,foreground_fraction,ymin,xmin,ymax,xmax   (the box columns empty for an empty mask)
+Classification: softmax of the [B, 2] logits on the device, one host copy at the end, OUT/predictions.csv: name,width,height,p0,p1,predicted.
+Rows come in file-name order.  No metric is computed and no label is read.  One process, one GPU.
+"""
+import argparse
+import importlib
+import json
+import os
+import sys
+import time
+from pathlib import Path
+
+sys.path.insert(0, str(Path(__file__).resolve().parents[2]))
+
+import torch
+
+ENTRIES = {"baselines": ("classification", "segmentation"), "biomedclip": ("classification", "segmentation"), "clip": ("classification", "segmentation"),
+           "clipseg": ("segmentation",), "dino": ("classification", "segmentation"), "metaclip": ("classification", "segmentation"),
+           "unimedclip": ("classification", "segmentation")}
+SEG_HEADER = "name,width,height,foreground_pixels,foreground_fraction,ymin,xmin,ymax,xmax"
+CLS_HEADER = "name,width,height,p0,p1,predicted"
+
+
+def split_argv(argv):
+    """argv -> (this module's arguments, the entry's own): the split at the first `--`."""
+    argv = list(argv)
+    if "--" in argv:
+        at = argv.index("--")
+        return argv[:at], argv[at + 1:]
+    return argv, []
+
+
+def get_args(argv=None):
+    own, rest = split_argv(sys.argv[1:] if argv is None else argv)
+    p = argparse.ArgumentParser("Masks or class probabilities for a directory of images, from a trained supervised entry")
+    p.add_argument("--entry", type=str, required=True, help="<family>.<segmentation|classification>, e.g. biomedclip.segmentation")
+    p.add_argument("--images", type=str, required=True, help="directory of .png .jpg .jpeg .bmp .tif .tiff files (not read recursively)")
+    p.add_argument("--out", type=str, required=True, help="output directory; must be absent or empty")
+    p.add_argument("--checkpoint", type=str, default=None, help="default: runs/<exp>/<dataset>/train/best_model.pth of the entry's flags")
+    p.add_argument("--overlay", default=True, action=argparse.BooleanOptionalAction, help="segmentation: write OUT/overlays/<stem>.png")
+    return p.parse_args(own), rest
+
+
+def entry_kind(name):
+    """"<family>.<kind>" -> (family, kind), or the refusal, by name."""
+    family, _, kind = str(name).partition(".")
+    if kind not in ENTRIES.get(family, ()):
+        known = ", ".join(f"{f}.{k}" for f, kinds in ENTRIES.items() for k in kinds)
+        raise ValueError(f"--entry {name}: prediction runs the supervised classification and segmentation entries only ({known}); the few-shot, fine-tune, "
+                         "zero-shot and retrieval modules have no checkpoint of that form")
+    return family, kind
+
+
+def default_checkpoint(entry_args):
+    return f"runs/{entry_args.exp}/{entry_args.dataset}/train/best_model.pth"
+
+
+def seg_csv(names, sizes, stats):
+    """names, [(H, W)], stats rows (foreground pixels, ymin, xmin, ymax, xmax, ...) -> the text of predictions.csv."""
+    lines = [SEG_HEADER]
+    for name, (H, W), s in zip(names, sizes, stats):
+        n, box = int(s[0]), ",".join(str(int(v)) for v in s[1:5]) if int(s[0]) > 0 else ",,,"
+        lines.append(f"{name},{W},{H},{n},{n / (H * W):.6f},{box}")
+    return "\n".join(lines) + "\n"
+
+
+def cls_csv(names, sizes, probs):
+    """names, [(H, W)], probabilities [n][2] -> the text of predictions.csv; `predicted` is the arg-max (a tie goes to class 0, as torch.argmax)."""
+    lines = [CLS_HEADER]
+    for name, (H, W), (p0, p1) in zip(names, sizes, probs):
+        lines.append(f"{name},{W},{H},{float(p0):.8f},{float(p1):.8f},{1 if float(p1) > float(p0) else 0}")
+    return "\n".join(lines) + "\n"
+
+
+def load_model(module, entry_args, checkpoint):
+    """The entry's model with the checkpoint in it, as its test() prepares it."""
+    from uia_hip import functional as UF
+    model = module.prepare_model(entry_args)
+    model.load_checkpoint(torch.load(checkpoint, map_location="cpu"))
+    UF.WEIGHTS.bump()
+    model.eval()
+    return model
+
+
+@torch.no_grad()
+def run(own, entry_args, module, kind):
+    from src.datasets import folder
+    from src.datasets.image_dir import ImageDirModule
+    from src.models import supervised
+    from src.utils.viz import NativeMaskWriter
+    from uia_hip import functional as UF
+
+    t0 = time.perf_counter()
+    seg = kind == "segmentation"
+    task = getattr(module, "TASK", supervised.SEGMENTATION if seg else supervised.CLASSIFICATION)
+    checkpoint = own.checkpoint or default_checkpoint(entry_args)
+    if not os.path.isdir(own.images):
+        raise FileNotFoundError(f"--images {own.images}: no such directory")
+    if os.path.exists(own.out) and (not os.path.isdir(own.out) or os.listdir(own.out)):
+        raise FileExistsError(f"--out {own.out} exists and is not an empty directory: nothing is overwritten")
+    if not os.path.isfile(checkpoint):
+        raise FileNotFoundError(f"checkpoint {checkpoint} not found (train the entry first, or pass --checkpoint)")
+    if hasattr(module, "check_args"):
+        module.check_args(entry_args)
+    dm = ImageDirModule(own.images, entry_args.img_size, entry_args.batch_size, getattr(entry_args, "num_workers", 0))
+    dm.start_workers()                                           # loader worker processes are forked BEFORE this process touches the GPU
+    ds = dm.dataset
+
+    torch.cuda.set_device(torch.device(entry_args.device))
+    UF.set_compute_dtype(torch.bfloat16 if entry_args.dtype == "bf16" else torch.float32)
+    model = load_model(module, entry_args, checkpoint)
+    prompt = getattr(module, "_batch_prompt", None)              # CLIPSeg: the per-batch prompt keyword function its test() hands to the loop
+    kwargs_for = prompt(entry_args) if prompt is not None else (lambda n: {})
+    os.makedirs(own.out, exist_ok=True)
+    writer = NativeMaskWriter(own.out, overlay=own.overlay) if seg else None
+    pf = folder.RaggedPrefetcher(dm.loader, entry_args.device)
+    resize = folder.ResizeStage(entry_args.img_size, with_mask=seg)
+    cur = torch.cuda.current_stream()
+    seen, probs, batches = 0, [], []
+    try:
+        for batch, second, ready in pf:
+            cur.wait_event(ready)
+            n = batch.desc.shape[0]
+            names = [ds.name_of(seen + j) for j in range(n)]    # the prefetcher drops names; the loader does not shuffle
+            seen += n
+            images, second = resize(batch, second)
+            images, _ = task.to_input(images, second, entry_args.in_channels)
+            logits = model(images, **kwargs_for(n)).detach()
+            if seg:
+                writer.submit(logits, batch, names)
+            else:
+                probs.append(torch.softmax(logits.float(), dim=1))
+        if seg:
+            batches, writer = writer.close(), None               # the writers are joined; a writer's exception surfaces here
+    finally:
+        if writer is not None:
+            writer.close()
+        pf.close()
+        dm.shutdown()
+    sizes = [(H, W) for W, H in ds.sizes]
+    if seg:
+        done = [name for b in batches for name in b[0]]
+        assert done == ds.names, "a batch is missing from the writers' results"
+        text = seg_csv(ds.names, sizes, [row for b in batches for row in b[2]])
+    else:
+        text = cls_csv(ds.names, sizes, torch.cat(probs).cpu().tolist())
+    with open(os.path.join(own.out, "predictions.csv"), "w") as f:
+        f.write(text)
+    return {"entry": own.entry, "images": len(ds), "out": own.out, "checkpoint": checkpoint, "seconds": round(time.perf_counter() - t0, 3)}
+
+
+def main(argv=None):
+    own, rest = get_args(argv)
+    family, kind = entry_kind(own.entry)                         # refused by name before anything of the entry is imported or built
+    module = importlib.import_module(f"src.models.{family}.{kind}")
+    entry_args = module.get_args(rest)
+    out = run(own, entry_args, module, kind)
+    print(json.dumps(out))
+    return out
+
+
+if __name__ == "__main__":
+    main()

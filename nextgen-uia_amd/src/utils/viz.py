@@ -127,3 +127,103 @@ class SegVisualizer:
             self._reap(wait=True)
         finally:
             self._jobs = []
+
+
+class NativeMaskWriter:
+    """The files of src/models/predict.py: per image `masks/<stem>.png` (8-bit grey, the image's own H x W) and, with overlay=True, `overlays/<stem>.png`
+    (RGB, the prediction in green over the grey input) under out_dir.  `submit` lays the batch's masks and overlays out back to back in one device
+    buffer, enqueues ONE launch of `uia_hip.ops.seg_predict_native` with the batch's own ragged source bytes, one copy of that buffer and one of the
+    statistics into a pinned slot, records an event and hands the slot to a writer thread (at most four), as SegVisualizer does.  The descriptor lives in
+    the slot, which goes back only behind the event.  `close()` joins the writers, re-raises a writer's exception and returns the batches' (names,
+    [(H, W)], stats int32 [n, 8]) in the order they were submitted."""
+
+    def __init__(self, out_dir, overlay=True, workers=MAX_WRITERS, level=PNG_LEVEL, device=None):
+        self.out_dir, self.overlay, self.level = Path(out_dir), bool(overlay), level
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        (self.out_dir / "masks").mkdir(parents=True, exist_ok=True)
+        if self.overlay:
+            (self.out_dir / "overlays").mkdir(parents=True, exist_ok=True)
+        workers = max(1, min(int(workers), MAX_WRITERS))
+        self._free = queue.Queue()
+        for _ in range(workers + 2):
+            self._free.put({"desc": None, "out": None, "stats": None})
+        self._dev_out = None
+        self._pool = ThreadPoolExecutor(max_workers=workers, thread_name_prefix="native-mask")
+        self._jobs, self._done = [], {}
+        self.files = self.bytes = self.batches = 0
+
+    @staticmethod
+    def layout(sizes, overlay):
+        """[(H, W)] -> ([(mask offset, overlay offset or -1)], total bytes): every image's mask, then its overlay, back to back."""
+        at, where = 0, []
+        for H, W in sizes:
+            moff, at = at, at + H * W
+            ooff = -1
+            if overlay:
+                ooff, at = at, at + 3 * H * W
+            where.append((moff, ooff))
+        return where, at
+
+    def submit(self, logits, batch, names):
+        """logits fp32 [n, 2, S, S] on the device, batch the folder.RaggedBatch the logits were computed from (its descriptor carries every image's
+        offset, H and W), n file names.  Enqueues on the current stream and returns; the files appear behind it."""
+        from uia_hip import ops
+        n = len(names)
+        if not (n > 0 and logits.shape[0] == n and batch.desc.shape[0] == n):
+            raise ValueError(f"NativeMaskWriter.submit: {n} names for {logits.shape[0]} predictions of {batch.desc.shape[0]} images")
+        self._reap()
+        geo = batch.desc[:, :3].tolist()
+        sizes = [(H, W) for _, H, W in geo]
+        where, total = self.layout(sizes, self.overlay)
+        slot = self._free.get()
+        if slot["desc"] is None or slot["desc"].shape[0] < n:
+            slot["desc"] = torch.empty(n, ops.SEG_NATIVE_DESC, dtype=torch.int32, pin_memory=True)
+            slot["stats"] = torch.empty(n, ops.SEG_NATIVE_DESC, dtype=torch.int32, pin_memory=True)
+        if slot["out"] is None or slot["out"].numel() < total:
+            slot["out"] = torch.empty(total + total // 4, dtype=torch.uint8, pin_memory=True)
+        if self._dev_out is None or self._dev_out.numel() < total:
+            self._dev_out = torch.empty(total + total // 4, dtype=torch.uint8, device=self.device)
+        desc = slot["desc"][:n]
+        desc.copy_(torch.tensor([[off if self.overlay else -1, H, W, moff, ooff, 0, 0, 0] for (off, H, W), (moff, ooff) in zip(geo, where)], dtype=torch.int32))
+        out = self._dev_out[:total]
+        stats = ops.seg_predict_native(logits.detach().float().contiguous(), batch.data if self.overlay else None, desc, out)
+        slot["out"][:total].copy_(out, non_blocking=True)
+        slot["stats"][:n].copy_(stats, non_blocking=True)
+        done = torch.cuda.Event()
+        done.record()
+        self._jobs.append(self._pool.submit(self._write, self.batches, done, slot, list(names), sizes, where))
+        self.batches += 1
+
+    def _write(self, k, done, slot, names, sizes, where):
+        try:
+            done.synchronize()
+            flat, size = slot["out"].numpy(), 0
+            for name, (H, W), (moff, ooff) in zip(names, sizes, where):
+                stem = str(Path(name).stem)
+                size += write_png(self.out_dir / "masks" / f"{stem}.png", flat[moff:moff + H * W].reshape(H, W), self.level)
+                if ooff >= 0:
+                    size += write_png(self.out_dir / "overlays" / f"{stem}.png", flat[ooff:ooff + 3 * H * W].reshape(H, W, 3), self.level)
+            return k, names, sizes, slot["stats"][:len(names)].clone().numpy(), (2 if self.overlay else 1) * len(names), size
+        finally:
+            self._free.put(slot)
+
+    def _reap(self, wait=False):
+        """Collects finished jobs; a writer's exception surfaces here."""
+        keep = []
+        for job in self._jobs:
+            if wait or job.done():
+                k, names, sizes, stats, files, size = job.result()
+                self._done[k] = (names, sizes, stats)
+                self.files, self.bytes = self.files + files, self.bytes + size
+            else:
+                keep.append(job)
+        self._jobs = keep
+
+    def close(self):
+        """Joins the writers; re-raises the first exception one of them met; -> [(names, [(H, W)], stats)] in submission order."""
+        try:
+            self._pool.shutdown(wait=True)
+            self._reap(wait=True)
+        finally:
+            self._jobs = []
+        return [self._done[k] for k in sorted(self._done)]

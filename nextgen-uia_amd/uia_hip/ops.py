@@ -2015,6 +2015,52 @@ def resize_batch_rgb(src, desc, S, out_images=None, ws=None):
     return out_images
 
 
+# ---------------------------------------------------------------- native-size masks from S x S logits (csrc/seg_native.hip)
+SEG_NATIVE_DESC = 8                        # int32 per image: source offset or -1, H, W, mask offset in out, overlay offset in out or -1, 0, 0, 0
+SEG_NATIVE_EMPTY = (0, 2 ** 31 - 1, 2 ** 31 - 1, -1, -1, 0, 0, 0)      # the stats row of an empty mask
+_SEG_NATIVE_WS = {}
+
+
+def seg_native_workspace(B, device):
+    """The scratch of uia_seg_predict_native on B images, kept per (device, stream, B): launches of one stream are ordered, so they may share it."""
+    need = lib().uia_seg_native_workspace_bytes(int(B))
+    if need == 0:
+        raise UiaError(f"seg_predict_native: B={B} is outside the kernel's limits (1 <= B <= 65535)")
+    key = (device.index if device.index is not None else torch.cuda.current_device(), torch.cuda.current_stream(device).cuda_stream, int(B))
+    ws = _SEG_NATIVE_WS.get(key)
+    if ws is None:
+        ws = _SEG_NATIVE_WS[key] = torch.empty(need, device=device, dtype=torch.uint8)
+    return ws
+
+
+def seg_predict_native(logits, src, desc, out, stats=None):
+    """logits fp32 [B, 2, S, S] on the device; src the batch's ragged 1-D uint8 device buffer (the one resize_batch read) or None when no image asks for an
+    overlay; desc a HOST int32 tensor [B, 8], per image (source offset or -1, H, W, mask offset in out, overlay offset in out or -1, 0, 0, 0) (pinned memory
+    makes its copy asynchronous, and it must then stay unchanged until the copy has run); out a 1-D uint8 device buffer -> stats int32 [B, 8] on the
+    device, per image (foreground pixels, ymin, xmin, ymax, xmax, 0, 0, 0) — SEG_NATIVE_EMPTY for an empty mask.  One launch writes into `out` every
+    image's H x W mask (255 where class 1 wins the bilinearly upsampled logits, torch's arg-max rule) and, where both offsets are given, its H x W x 3
+    overlay (g, max(g, p), g).  Enqueued only: nothing is read back."""
+    _p(logits), _p(src), _p(out), _p(stats)
+    if logits.dim() != 4 or logits.shape[1] != 2 or logits.shape[2] != logits.shape[3] or logits.dtype != torch.float32 or not logits.is_contiguous():
+        raise UiaError(f"seg_predict_native: logits must be contiguous fp32 [B, 2, S, S], got {logits.dtype} {tuple(logits.shape)}")
+    B, _, S, _ = logits.shape
+    for t, name in ((src, "src"), (out, "out")):
+        if t is not None and (t.dim() != 1 or t.dtype != torch.uint8 or not t.is_contiguous() or t.device != logits.device):
+            raise UiaError(f"seg_predict_native: {name} must be a contiguous 1-D uint8 tensor on the logits' device, got {t.dtype} {tuple(t.shape)}")
+    if out is None:
+        raise UiaError("seg_predict_native: out is required (the caller lays the masks and overlays out in it)")
+    if (not isinstance(desc, torch.Tensor) or desc.is_cuda or desc.dtype != torch.int32 or tuple(desc.shape) != (B, SEG_NATIVE_DESC) or not desc.is_contiguous()):
+        raise UiaError(f"seg_predict_native: desc must be a contiguous host int32 tensor [{B}, {SEG_NATIVE_DESC}]")
+    if stats is None:
+        stats = torch.empty((B, SEG_NATIVE_DESC), dtype=torch.int32, device=logits.device)
+    if tuple(stats.shape) != (B, SEG_NATIVE_DESC) or stats.dtype != torch.int32 or not stats.is_contiguous() or stats.device != logits.device:
+        raise UiaError(f"seg_predict_native: stats must be contiguous int32 [{B}, {SEG_NATIVE_DESC}] on the logits' device")
+    ws = seg_native_workspace(B, logits.device)
+    check(lib().uia_seg_predict_native(_stream(), B, S, _p(logits), _p(src), 0 if src is None else src.numel(), desc.data_ptr(), _p(out), out.numel(), _p(ws),
+                                       ws.numel(), _p(stats)), "uia_seg_predict_native")
+    return stats
+
+
 # ---------------------------------------------------------------- DINOv2 UNet decoder (csrc/unet_conv.hip, unet_bn.hip, unet_resample.hip)
 CONV3, CONVT_FWD, CONVT_BWD, CONV1 = 0, 1, 2, 3      # uia_conv_igemm / uia_conv_wgrad modes
 BN_SLICES = 256                            # UIA_BN_SLICES
