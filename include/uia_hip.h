@@ -631,6 +631,28 @@ size_t uia_seg_native_workspace_bytes(int B);
 int uia_seg_predict_native(void* stream, int B, int S, const float* logits, const uint8_t* src, size_t src_bytes, const int32_t* desc, uint8_t* out,
                            size_t out_bytes, void* ws, size_t ws_bytes, int32_t* stats);
 
+/* Connected-component filtering of native-size masks where they lie, and one row per kept lesion (csrc/components.hip).  buf: one DEVICE byte buffer of
+ * buf_bytes bytes (< 2^31), in the prediction path the `out` buffer of uia_seg_predict_native as it returned.  desc: a HOST array int32 [B][8], per image
+ * (mask_offset, H, W, overlay_offset or -1, min_area, keep, connectivity, 0); offsets are arbitrary bytes.  A mask byte != 0 is foreground; components
+ * are 4- or 8-connected per `connectivity`; a component's first pixel is its smallest raster index y * W + x; components are ordered by area, largest
+ * first, equal areas by smaller first pixel first; a component is kept when area >= min_area and (keep == 0 or its position in that order < keep).
+ * Written: every pixel of a component that is not kept gets mask byte 0 and, with an overlay, overlay byte[1] = byte[0] (the overlay is
+ * (g, max(g, p), g)); kept pixels and background keep their bytes.  stats: DEVICE int32 [B][8] = (foreground after, ymin, xmin, ymax, xmax after,
+ * components found, components kept, foreground before), the box of an empty result (INT_MAX, INT_MAX, -1, -1): words 0-4 mean what they mean in
+ * uia_seg_predict_native.  list: DEVICE int32 [B][max_list][8], 0 <= max_list <= 32 (NULL allowed at 0): the first max_list kept components in that
+ * order, each (area, ymin, xmin, ymax, xmax, first pixel, floor(sum y / area), floor(sum x / area)) with 64-bit sums; unused rows are zeros.  Every
+ * word of stats and list is written; nothing beside them, the mask bytes and the overlays' green bytes is touched.
+ * Checked before anything is enqueued (non-zero, nothing written, the image's index in uia_last_error()): 1 <= B <= 65535, 1 <= H, W <= 16384, null
+ * buf / desc / ws / stats, a null list with max_list > 0, max_list outside 0 .. 32, a connectivity other than 4 or 8, a negative min_area or keep, a
+ * non-zero reserved word, a mask or overlay that leaves buf, ranges that overlap each other, stats, list or the workspace, a workspace below
+ * uia_mask_components_workspace_bytes(B, pixels) with pixels = the sum of H * W over the batch (0 for arguments outside the limits; 8-byte aligned;
+ * 8 bytes per pixel and about 3.4 KiB per image).  The descriptor is then copied to the workspace with hipMemcpyAsync on `stream`, so a pinned
+ * descriptor must stay as it is until that copy has run.  Asynchronous, no host synchronisation; integer atomics only, so two calls on equal input
+ * give identical bytes whatever the scheduling. */
+size_t uia_mask_components_workspace_bytes(int B, int64_t pixels);
+int uia_mask_components(void* stream, int B, uint8_t* buf, size_t buf_bytes, const int32_t* desc, void* ws, size_t ws_bytes, int32_t* stats, int32_t* list,
+                        int max_list);
+
 /* ---------------------------------------------------------------------------------------------
  * Layout helpers around the GEMMs. */
 int uia_cast(void* stream, int dtype, size_t n, const float* src, void* dst, float scale);          /* dst = T(scale*src) */

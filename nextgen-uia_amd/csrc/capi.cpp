@@ -297,6 +297,11 @@ int uia_seg_predict_native(void* stream, int B, int S, const float* logits, cons
     return uia_seg_predict_native_launch((hipStream_t)stream, B, S, logits, src, src_bytes, desc, out, out_bytes, ws, ws_bytes, stats);
 }
 
+size_t uia_mask_components_workspace_bytes(int B, int64_t pixels) { return uia_mask_components_ws_bytes(B, pixels); }
+int uia_mask_components(void* stream, int B, uint8_t* buf, size_t buf_bytes, const int32_t* desc, void* ws, size_t ws_bytes, int32_t* stats, int32_t* list, int max_list) {
+    return uia_mask_components_launch((hipStream_t)stream, B, buf, buf_bytes, desc, ws, ws_bytes, stats, list, max_list);
+}
+
 int uia_im2col_padded(void* stream, int dtype, int B, int C, int H, int W, int P, const float* img, void* cols, int64_t ldo) {
     return uia_im2col_padded_launch((hipStream_t)stream, dtype, B, C, H, W, P, img, cols, (long)ldo);
 }

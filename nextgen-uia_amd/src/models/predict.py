@@ -15,6 +15,12 @@ one pinned copy back -> at most four writer threads (src/utils/viz.NativeMaskWri
     OUT/predictions.csv        name,width,height,foreground_pixels,foreground_fraction,ymin,xmin,ymax,xmax   (the box columns empty for an empty mask)
 Classification: softmax of the [B, 2] logits on the device, one host copy at the end, OUT/predictions.csv: name,width,height,p0,p1,predicted.
 Rows come in file-name order.  No metric is computed and no label is read.  One process, one GPU.
+
+Segmentation only: --min_area N (components below N pixels leave the mask), --keep_largest K (only the K largest stay), --connectivity {4,8} and
+--lesions K (0 .. 32) label the masks on the device (uia_hip.ops.mask_components, one call per batch behind the launch above) before they are copied
+back: masks, overlays and predictions.csv then describe the filtered mask, and with --lesions K > 0
+    OUT/lesions.csv            name,lesion,area,ymin,xmin,ymax,xmax,cy,cx     one row per kept component, at most K per picture, largest first, numbered
+                                                                              from 1 (equal areas: the one whose first pixel comes first); none for an empty mask
 """
 import argparse
 import importlib
@@ -33,6 +39,9 @@ ENTRIES = {"baselines": ("classification", "segmentation"), "biomedclip": ("clas
            "unimedclip": ("classification", "segmentation")}
 SEG_HEADER = "name,width,height,foreground_pixels,foreground_fraction,ymin,xmin,ymax,xmax"
 CLS_HEADER = "name,width,height,p0,p1,predicted"
+LESION_HEADER = "name,lesion,area,ymin,xmin,ymax,xmax,cy,cx"
+MAX_LESIONS = 32
+COMPONENT_FLAGS = {"min_area": ("--min_area", 0), "keep_largest": ("--keep_largest", 0), "connectivity": ("--connectivity", 8), "lesions": ("--lesions", 0)}
 
 
 def split_argv(argv):
@@ -52,7 +61,22 @@ def get_args(argv=None):
     p.add_argument("--out", type=str, required=True, help="output directory; must be absent or empty")
     p.add_argument("--checkpoint", type=str, default=None, help="default: runs/<exp>/<dataset>/train/best_model.pth of the entry's flags")
     p.add_argument("--overlay", default=True, action=argparse.BooleanOptionalAction, help="segmentation: write OUT/overlays/<stem>.png")
+    p.add_argument("--min_area", type=int, default=0, help="segmentation: components of fewer pixels leave the mask (0 or 1: none does)")
+    p.add_argument("--keep_largest", type=int, default=0, help="segmentation: only the K largest components stay (0: any number)")
+    p.add_argument("--connectivity", type=int, default=8, choices=(4, 8), help="segmentation: what joins two pixels into one component")
+    p.add_argument("--lesions", type=int, default=0, help=f"segmentation: write OUT/lesions.csv with the K <= {MAX_LESIONS} largest kept components of every picture")
     return p.parse_args(own), rest
+
+
+def check_components(own, kind):
+    """The component flags are for segmentation and within the kernel's limits: refused by name before anything of the entry is imported."""
+    given = [flag for key, (flag, default) in COMPONENT_FLAGS.items() if getattr(own, key) != default]
+    if kind != "segmentation" and given:
+        raise ValueError(f"--entry {own.entry}: {', '.join(given)} filter segmentation masks; a classification entry has none")
+    if own.min_area < 0 or own.keep_largest < 0:
+        raise ValueError(f"--min_area {own.min_area} / --keep_largest {own.keep_largest}: neither may be negative")
+    if not 0 <= own.lesions <= MAX_LESIONS:
+        raise ValueError(f"--lesions {own.lesions}: 0 .. {MAX_LESIONS}")
 
 
 def entry_kind(name):
@@ -75,6 +99,18 @@ def seg_csv(names, sizes, stats):
     for name, (H, W), s in zip(names, sizes, stats):
         n, box = int(s[0]), ",".join(str(int(v)) for v in s[1:5]) if int(s[0]) > 0 else ",,,"
         lines.append(f"{name},{W},{H},{n},{n / (H * W):.6f},{box}")
+    return "\n".join(lines) + "\n"
+
+
+def lesions_csv(names, lists):
+    """names, per image rows (area, ymin, xmin, ymax, xmax, first pixel, cy, cx) with zero rows unused -> the text of lesions.csv: one row per kept
+    component, numbered from 1 in the kernel's order; a picture without one gets no row."""
+    lines = [LESION_HEADER]
+    for name, rows in zip(names, lists):
+        for k, r in enumerate(rows):
+            if int(r[0]) <= 0:
+                break
+            lines.append(f"{name},{k + 1},{int(r[0])},{int(r[1])},{int(r[2])},{int(r[3])},{int(r[4])},{int(r[6])},{int(r[7])}")
     return "\n".join(lines) + "\n"
 
 
@@ -126,11 +162,12 @@ def run(own, entry_args, module, kind):
     prompt = getattr(module, "_batch_prompt", None)              # CLIPSeg: the per-batch prompt keyword function its test() hands to the loop
     kwargs_for = prompt(entry_args) if prompt is not None else (lambda n: {})
     os.makedirs(own.out, exist_ok=True)
-    writer = NativeMaskWriter(own.out, overlay=own.overlay) if seg else None
+    writer = NativeMaskWriter(own.out, overlay=own.overlay, min_area=own.min_area, keep=own.keep_largest, connectivity=own.connectivity,
+                              lesions=own.lesions) if seg else None
     pf = folder.RaggedPrefetcher(dm.loader, entry_args.device)
     resize = folder.ResizeStage(entry_args.img_size, with_mask=seg)
     cur = torch.cuda.current_stream()
-    seen, probs, batches = 0, [], []
+    seen, probs, batches, lists = 0, [], [], []
     try:
         for batch, second, ready in pf:
             cur.wait_event(ready)
@@ -145,7 +182,7 @@ def run(own, entry_args, module, kind):
             else:
                 probs.append(torch.softmax(logits.float(), dim=1))
         if seg:
-            batches, writer = writer.close(), None               # the writers are joined; a writer's exception surfaces here
+            batches, lists, writer = writer.close(), writer.lesion_lists(), None     # the writers are joined; a writer's exception surfaces here
     finally:
         if writer is not None:
             writer.close()
@@ -156,6 +193,9 @@ def run(own, entry_args, module, kind):
         done = [name for b in batches for name in b[0]]
         assert done == ds.names, "a batch is missing from the writers' results"
         text = seg_csv(ds.names, sizes, [row for b in batches for row in b[2]])
+        if own.lesions > 0:
+            with open(os.path.join(own.out, "lesions.csv"), "w") as f:
+                f.write(lesions_csv(ds.names, [rows for b in lists for rows in b]))
     else:
         text = cls_csv(ds.names, sizes, torch.cat(probs).cpu().tolist())
     with open(os.path.join(own.out, "predictions.csv"), "w") as f:
@@ -166,6 +206,7 @@ def run(own, entry_args, module, kind):
 def main(argv=None):
     own, rest = get_args(argv)
     family, kind = entry_kind(own.entry)                         # refused by name before anything of the entry is imported or built
+    check_components(own, kind)
     module = importlib.import_module(f"src.models.{family}.{kind}")
     entry_args = module.get_args(rest)
     out = run(own, entry_args, module, kind)

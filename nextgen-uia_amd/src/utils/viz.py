@@ -135,10 +135,21 @@ class NativeMaskWriter:
     buffer, enqueues ONE launch of `uia_hip.ops.seg_predict_native` with the batch's own ragged source bytes, one copy of that buffer and one of the
     statistics into a pinned slot, records an event and hands the slot to a writer thread (at most four), as SegVisualizer does.  The descriptor lives in
     the slot, which goes back only behind the event.  `close()` joins the writers, re-raises a writer's exception and returns the batches' (names,
-    [(H, W)], stats int32 [n, 8]) in the order they were submitted."""
+    [(H, W)], stats int32 [n, 8]) in the order they were submitted.
 
-    def __init__(self, out_dir, overlay=True, workers=MAX_WRITERS, level=PNG_LEVEL, device=None):
+    min_area / keep / connectivity / lesions: connected-component filtering on the device.  With all four at their defaults nothing else is enqueued.
+    Otherwise ONE `uia_hip.ops.mask_components` call on the device buffer follows the launch, before the copies: components below min_area pixels and
+    those beyond the `keep` largest (0 = any number) leave masks and overlays, the slot's stats are that call's (words 0-4 keep their meaning, 5-7 are
+    components found, kept and the foreground before), and the first `lesions` (<= 32) kept components of every image are copied into the slot as well:
+    `lesion_lists()` returns them after `close()`, int32 [n, lesions, 8] per batch in submission order."""
+
+    def __init__(self, out_dir, overlay=True, workers=MAX_WRITERS, level=PNG_LEVEL, device=None, min_area=0, keep=0, connectivity=8, lesions=0):
         self.out_dir, self.overlay, self.level = Path(out_dir), bool(overlay), level
+        self.min_area, self.keep, self.connectivity, self.lesions = int(min_area), int(keep), int(connectivity), int(lesions)
+        if self.min_area < 0 or self.keep < 0 or self.connectivity not in (4, 8) or not 0 <= self.lesions <= 32:
+            raise ValueError(f"NativeMaskWriter: min_area={min_area}, keep={keep} (>= 0), connectivity={connectivity} (4 or 8), lesions={lesions} (0 .. 32)")
+        self.components = (self.min_area, self.keep, self.connectivity, self.lesions) != (0, 0, 8, 0)
+        self._lists = {}
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         (self.out_dir / "masks").mkdir(parents=True, exist_ok=True)
         if self.overlay:
@@ -146,7 +157,7 @@ class NativeMaskWriter:
         workers = max(1, min(int(workers), MAX_WRITERS))
         self._free = queue.Queue()
         for _ in range(workers + 2):
-            self._free.put({"desc": None, "out": None, "stats": None})
+            self._free.put({"desc": None, "out": None, "stats": None, "cdesc": None, "list": None})
         self._dev_out = None
         self._pool = ThreadPoolExecutor(max_workers=workers, thread_name_prefix="native-mask")
         self._jobs, self._done = [], {}
@@ -187,6 +198,15 @@ class NativeMaskWriter:
         desc.copy_(torch.tensor([[off if self.overlay else -1, H, W, moff, ooff, 0, 0, 0] for (off, H, W), (moff, ooff) in zip(geo, where)], dtype=torch.int32))
         out = self._dev_out[:total]
         stats = ops.seg_predict_native(logits.detach().float().contiguous(), batch.data if self.overlay else None, desc, out)
+        if self.components:
+            if slot["cdesc"] is None or slot["cdesc"].shape[0] < n:
+                slot["cdesc"] = torch.empty(n, ops.MASK_COMPONENTS_DESC, dtype=torch.int32, pin_memory=True)
+                slot["list"] = torch.empty(n, self.lesions, 8, dtype=torch.int32, pin_memory=True)
+            cdesc = slot["cdesc"][:n]
+            cdesc.copy_(torch.tensor([[moff, H, W, ooff, self.min_area, self.keep, self.connectivity, 0] for (H, W), (moff, ooff) in zip(sizes, where)],
+                                     dtype=torch.int32))
+            stats, rows = ops.mask_components(out, cdesc, self.lesions)
+            slot["list"][:n].copy_(rows, non_blocking=True)
         slot["out"][:total].copy_(out, non_blocking=True)
         slot["stats"][:n].copy_(stats, non_blocking=True)
         done = torch.cuda.Event()
@@ -203,6 +223,8 @@ class NativeMaskWriter:
                 size += write_png(self.out_dir / "masks" / f"{stem}.png", flat[moff:moff + H * W].reshape(H, W), self.level)
                 if ooff >= 0:
                     size += write_png(self.out_dir / "overlays" / f"{stem}.png", flat[ooff:ooff + 3 * H * W].reshape(H, W, 3), self.level)
+            if self.components:
+                self._lists[k] = slot["list"][:len(names)].clone().numpy()
             return k, names, sizes, slot["stats"][:len(names)].clone().numpy(), (2 if self.overlay else 1) * len(names), size
         finally:
             self._free.put(slot)
@@ -227,3 +249,8 @@ class NativeMaskWriter:
         finally:
             self._jobs = []
         return [self._done[k] for k in sorted(self._done)]
+
+    def lesion_lists(self):
+        """After close(): per batch, in submission order, int32 [n, lesions, 8] — per image the first `lesions` kept components, largest first, as rows
+        (area, ymin, xmin, ymax, xmax, first pixel, cy, cx), unused rows zero.  Empty when the writer filters nothing."""
+        return [self._lists[k] for k in sorted(self._lists)]

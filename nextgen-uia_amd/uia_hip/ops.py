@@ -2061,6 +2061,51 @@ def seg_predict_native(logits, src, desc, out, stats=None):
     return stats
 
 
+# ---------------------------------------------------------------- connected components of native-size masks (csrc/components.hip)
+MASK_COMPONENTS_DESC = 8                   # int32 per image: mask offset, H, W, overlay offset or -1, min_area, keep, connectivity (4 | 8), 0
+MASK_COMPONENTS_MAX_LIST = 32
+_MASK_COMPONENTS_WS = {}
+
+
+def mask_components_workspace(B, pixels, device):
+    """The scratch of uia_mask_components on B images of `pixels` pixels in all, kept per (device, stream) and grown when a batch needs more: launches of
+    one stream are ordered, so they may share it."""
+    need = lib().uia_mask_components_workspace_bytes(int(B), int(pixels))
+    if need == 0:
+        raise UiaError(f"mask_components: B={B}, pixels={pixels} is outside the kernel's limits (1 <= B <= 65535, 1 <= pixels < 2^31)")
+    key = (device.index if device.index is not None else torch.cuda.current_device(), torch.cuda.current_stream(device).cuda_stream)
+    ws = _MASK_COMPONENTS_WS.get(key)
+    if ws is None or ws.numel() < need:
+        ws = _MASK_COMPONENTS_WS[key] = torch.empty(need + need // 4, device=device, dtype=torch.uint8)
+    return ws
+
+
+def mask_components(buf, desc, max_list=0):
+    """buf a 1-D uint8 device buffer holding the batch's masks (and overlays), e.g. the `out` of seg_predict_native; desc a HOST int32 tensor [B, 8], per
+    image (mask offset, H, W, overlay offset or -1, min_area, keep, connectivity, 0) (pinned memory makes its copy asynchronous, and it must then stay
+    unchanged until the copy has run) -> (stats int32 [B, 8], list int32 [B, max_list, 8]) on the device.  In place: every pixel of a 4- / 8-connected
+    component that is not kept (area >= min_area, and among the `keep` largest when keep > 0; equal areas by first pixel) gets mask byte 0 and its
+    overlay's green byte the red one.  stats = (foreground after, ymin, xmin, ymax, xmax, components found, components kept, foreground before); list rows
+    = (area, ymin, xmin, ymax, xmax, first pixel, cy, cx) of the first max_list kept components, largest first, unused rows zero.  Enqueued only."""
+    _p(buf)
+    if buf is None or buf.dim() != 1 or buf.dtype != torch.uint8 or not buf.is_contiguous() or not buf.is_cuda:
+        raise UiaError("mask_components: buf must be a contiguous 1-D uint8 tensor on the device")
+    if (not isinstance(desc, torch.Tensor) or desc.is_cuda or desc.dtype != torch.int32 or desc.dim() != 2 or desc.shape[1] != MASK_COMPONENTS_DESC
+            or desc.shape[0] < 1 or not desc.is_contiguous()):
+        raise UiaError(f"mask_components: desc must be a contiguous host int32 tensor [B, {MASK_COMPONENTS_DESC}]")
+    max_list = int(max_list)
+    if not 0 <= max_list <= MASK_COMPONENTS_MAX_LIST:
+        raise UiaError(f"mask_components: max_list={max_list} (0 .. {MASK_COMPONENTS_MAX_LIST})")
+    B = desc.shape[0]
+    pixels = int((desc[:, 1].long().clamp(min=0) * desc[:, 2].long().clamp(min=0)).sum())
+    stats = torch.empty((B, 8), dtype=torch.int32, device=buf.device)
+    rows = torch.empty((B, max_list, 8), dtype=torch.int32, device=buf.device)
+    ws = mask_components_workspace(B, max(1, min(pixels, 2 ** 31 - 1)), buf.device)     # (a descriptor outside the limits is refused by the launcher, by image)
+    check(lib().uia_mask_components(_stream(), B, _p(buf), buf.numel(), desc.data_ptr(), _p(ws), ws.numel(), _p(stats), _p(rows) if max_list else None, max_list),
+          "uia_mask_components")
+    return stats, rows
+
+
 # ---------------------------------------------------------------- DINOv2 UNet decoder (csrc/unet_conv.hip, unet_bn.hip, unet_resample.hip)
 CONV3, CONVT_FWD, CONVT_BWD, CONV1 = 0, 1, 2, 3      # uia_conv_igemm / uia_conv_wgrad modes
 BN_SLICES = 256                            # UIA_BN_SLICES
