@@ -591,14 +591,16 @@ __global__ __launch_bounds__(512) void mona_spatial_kernel(const uia_mona_spatia
         dwm2 = fmaf(dcv, fmaf(f, s2, b2), dwm2);
         dwm3 = fmaf(dcv, fmaf(f, s3, b3), dwm3);
     }
-    // reduce over the pixel groups with LDS atomics into [64][50] (the c tile is free now)
+    // reduce over the pixel groups into [64][50] (the c tile is free now), one group after the other with group 0 storing: a fixed order, so
+    // that two launches with a workspace return the same bits (LDS float atomics from the eight waves met in any order and did not)
     float* red = cS;
-    for (int i = tid; i < RED_FLOATS; i += 512) red[i] = 0.f;
-    __syncthreads();
+    for (int q = 0; q < NGRP; ++q) {
+        if (grp == q) {
 #pragma unroll
-    for (int i = 0; i < 49; ++i) atomicAdd(red + c * 50 + i, dkm[i]);
-    atomicAdd(red + c * 50 + 49, sdc);
-    __syncthreads();
+            for (int i = 0; i < 50; ++i) { const float v = i < 49 ? dkm[i] : sdc; red[c * 50 + i] = q ? red[c * 50 + i] + v : v; }
+        }
+        __syncthreads();
+    }
     if (grp == 0) {
 #pragma unroll
         for (int i = 0; i < 49; ++i) dkm[i] = f * red[c * 50 + i];      // Σ dc·xf[nbr]
@@ -696,7 +698,8 @@ __global__ __launch_bounds__(512) void mona_spatial_kernel(const uia_mona_spatia
 //     read from LDS once (W loads) into a zero-padded register strip and feeds 7·W FMAs with compile-time indices.
 //     (The per-pixel form spent ~4 VALU instructions of bounds logic and one LDS load per FMA.)
 //   * the 1×1 projector, its data gradient and its weight gradient run on the matrix cores
-//     (v_mfma_f32_16x16x32_bf16, operands converted from the fp32 LDS tiles on the way into the registers).
+//     (v_mfma_f32_16x16x32_bf16, operands converted from the fp32 LDS tiles on the way into the registers; the weight
+//     gradient, a sum over pixels that can be short, takes them as hi + lo pairs).
 //     c and dz tiles use a row stride of 68 floats so that row-per-lane fragment reads are conflict-free.
 template <int W, bool BWD>
 __global__ __launch_bounds__(512) void mona_spatial_fast_kernel(const uia_mona_spatial_desc p) {
@@ -835,19 +838,27 @@ __global__ __launch_bounds__(512) void mona_spatial_fast_kernel(const uia_mona_s
         const int mt = grp & 3, nt0 = 2 * (grp >> 2);
         f32x4 acc[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
         const int ksteps = (hw + 31) >> 5;
+        // Each fp32 operand goes in as hi + lo (two bf16 values, 16 significant bits) and a product as hi·hi + hi·lo + lo·hi: 3·2^-16 of |dz||c| instead
+        // of the 2·2^-8 of two operands rounded once.  With few pixels and images the sum has few terms and a single rounding of each operand showed in
+        // the gradient itself (0.8 % at 1 x 4, B = 2); the phase is 7 k-steps at 14 x 14 and the two further MFMAs per tile do not move the step's time.
         for (int ks = 0; ks < ksteps; ++ks) {
-            bf16x8 a, bb[2];
+            bf16x8 a, al, bb[2], bl[2];
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 const int px = 32 * ks + 8 * g + e;
                 const int pc = px < hw ? px : hw - 1;
-                const float av = gS[(1 + pc) * FLD + 16 * mt + li];
-                a[e] = (bf16_t)(px < hw ? av : 0.f);
-                bb[0][e] = (bf16_t)cS[pc * FLD + 16 * nt0 + li];
-                bb[1][e] = (bf16_t)cS[pc * FLD + 16 * (nt0 + 1) + li];
+                const float av = px < hw ? gS[(1 + pc) * FLD + 16 * mt + li] : 0.f;
+                const float b0 = cS[pc * FLD + 16 * nt0 + li], b1 = cS[pc * FLD + 16 * (nt0 + 1) + li];
+                a[e] = (bf16_t)av;      al[e] = (bf16_t)(av - (float)a[e]);
+                bb[0][e] = (bf16_t)b0;  bl[0][e] = (bf16_t)(b0 - (float)bb[0][e]);
+                bb[1][e] = (bf16_t)b1;  bl[1][e] = (bf16_t)(b1 - (float)bb[1][e]);
             }
-            acc[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, bb[0], acc[0], 0, 0, 0);
-            acc[1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, bb[1], acc[1], 0, 0, 0);
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {
+                acc[q] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al, bb[q], acc[q], 0, 0, 0);
+                acc[q] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, bl[q], acc[q], 0, 0, 0);
+                acc[q] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, bb[q], acc[q], 0, 0, 0);
+            }
         }
 #pragma unroll
         for (int q = 0; q < 2; ++q)
