@@ -134,6 +134,10 @@ typedef struct uia_gemm_desc {
      * nearest: the T copy the next GEMM reads as its A operand anyway) plus lo = the next 8 mantissa bits as a signed byte,
      *     float_bits(x) ≈ (hi_bits << 16) + (lo << 8)      (15 stored mantissa bits: 2^-16 relative),
      * so a sub-layer sum costs 3 + 3 bytes per element in the epilogue that reads one and writes the next, instead of 4 + (4 + 2).
+     * lo = ((bits + 0x80) >> 8) - (hi_bits << 8) lies in [-128, 128] and is clamped to +-127: the decoded value is within 2^-16 of x (relative)
+     * where the clamp did not act, within 2^-15 where it did (1 value in 256), within 256 * 2^-149 (absolute) for subnormal x.
+     * INPUT CONDITION: |x| below the float with bits 0x7F7F8000 (3.39618e38).  From there on the round-to-nearest hi plane is inf (the T copy a
+     * GEMM reads), and from bits 0x7F7FFF80 on the decoded value is inf too, although x is finite.  (tests/layernorm_reference.py proves the figures.)
      *   resid_lo8 != NULL: the residual is (residT, resid_lo8) in that form — residT row-major (ldrT) or, residT_kb_rows > 0, K-blocked like
      *                      outT; `resid` must be NULL; resid_ln_* (stats / weight / bias / dim) then apply to the reconstructed rows.
      *   out_lo8   != NULL: the result's low bytes go there (row-major, ld_out_lo), its hi plane is outT (required); out32 may be NULL.
