@@ -635,6 +635,33 @@ size_t uia_seg_native_workspace_bytes(int B);
 int uia_seg_predict_native(void* stream, int B, int S, const float* logits, const uint8_t* src, size_t src_bytes, const int32_t* desc, uint8_t* out,
                            size_t out_bytes, void* ws, size_t ws_bytes, int32_t* stats);
 
+/* uia_seg_predict_native for an ensemble of K members (checkpoints, flips of the model's input, or both), with a threshold the caller sets, a
+ * probability map and a spread map: one launch per batch (csrc/seg_native_ens.hip).  logits fp32 [K][B][2][S][S], contiguous, 4-byte aligned,
+ * 1 <= K <= 16.  flips holds two bits per member: bit 2k says that member k's logits are of the horizontally flipped S x S input, bit 2k + 1 the same
+ * for a vertical flip; the kernel reads member k's planes as L'_c[y][x] = L_c[fy ? S - 1 - y : y][fx ? S - 1 - x : x]; bits at or above 2 K must be
+ * zero.  threshold: a finite float with 0 < threshold < 1.  src, out, stats, the limits on B, S, H, W and the buffer sizes: uia_seg_predict_native's.
+ * desc: a HOST array int32 [B][8], per image (src_offset or -1, H, W, mask_out_offset, overlay_out_offset or -1, probability_out_offset or -1,
+ * spread_out_offset or -1, 0); offsets are arbitrary bytes, no alignment is asked.  sums: DEVICE uint64 [B][2], 8-byte aligned, or NULL.
+ * Per native pixel and member k, u_0 and u_1 are computed from L' exactly as uia_seg_predict_native computes them (the same coordinates, rows first,
+ * then columns, a tap of weight exactly 0 left out, every product and sum rounded once in fp32); z_k = u_1 - u_0, p_k = 1 / (1 + expf(-z_k)) with an
+ * IEEE division; P = (p_0 + ... + p_{K-1}) / K, summed in member order in fp32.
+ * Outputs: the mask, 255 where P > threshold (strictly), else 0; the overlay (g, max(g, mask), g) as uia_seg_predict_native's; at the probability
+ * offset H * W bytes q = (uint8)(255 P + 0.5f); at the spread offset H * W bytes r = (uint8)(255 (max_k p_k - min_k p_k) + 0.5f), 0 at K = 1.  A pixel
+ * where any z_k is NaN gets mask 0, q = 0, r = 255; infinite logits follow IEEE (z = +inf gives p = 1, -inf gives 0, inf - inf is NaN).
+ * stats[b] = (foreground count, ymin, xmin, ymax, xmax, 0, 0, 0) with uia_seg_predict_native's empty value, set by the call itself, so
+ * uia_mask_components reads the result unchanged.  sums[b] = (sum of q over the pixels whose mask byte this launch wrote as 255, sum of r over all
+ * pixels), zeroed by the call and accumulated with 64-bit integer atomics, computed whether or not the map is stored.
+ * Asynchronous, deterministic (integer atomics only: two calls give identical bytes).  Every byte of the requested ranges, of stats and of sums is
+ * written, nothing beside them.
+ * Checked before anything is enqueued (non-zero, nothing written, the image's index in uia_last_error()): everything uia_seg_predict_native checks,
+ * K outside 1 .. 16, stray flip bits, a threshold outside (0, 1) or NaN, a misaligned sums, a probability or spread map that leaves `out` or overlaps
+ * any other range, src, logits, stats, sums or the workspace, a non-zero reserved word (word 7).  The descriptor is then copied to the workspace with
+ * hipMemcpyAsync on `stream`, so a pinned descriptor must stay as it is until that copy has run.  ws: uia_seg_native_ens_workspace_bytes(B) of 4-byte
+ * aligned scratch (0 for a B outside the limits): the device copy of the descriptor. */
+size_t uia_seg_native_ens_workspace_bytes(int B);
+int uia_seg_predict_native_ens(void* stream, int K, int B, int S, const float* logits, uint32_t flips, float threshold, const uint8_t* src, size_t src_bytes,
+                               const int32_t* desc, uint8_t* out, size_t out_bytes, void* ws, size_t ws_bytes, int32_t* stats, uint64_t* sums);
+
 /* Connected-component filtering of native-size masks where they lie, and one row per kept lesion (csrc/components.hip).  buf: one DEVICE byte buffer of
  * buf_bytes bytes (< 2^31), in the prediction path the `out` buffer of uia_seg_predict_native as it returned.  desc: a HOST array int32 [B][8], per image
  * (mask_offset, H, W, overlay_offset or -1, min_area, keep, connectivity, 0); offsets are arbitrary bytes.  A mask byte != 0 is foreground; components

@@ -297,6 +297,12 @@ int uia_seg_predict_native(void* stream, int B, int S, const float* logits, cons
     return uia_seg_predict_native_launch((hipStream_t)stream, B, S, logits, src, src_bytes, desc, out, out_bytes, ws, ws_bytes, stats);
 }
 
+size_t uia_seg_native_ens_workspace_bytes(int B) { return uia_seg_native_ens_ws_bytes(B); }
+int uia_seg_predict_native_ens(void* stream, int K, int B, int S, const float* logits, uint32_t flips, float threshold, const uint8_t* src, size_t src_bytes,
+                               const int32_t* desc, uint8_t* out, size_t out_bytes, void* ws, size_t ws_bytes, int32_t* stats, uint64_t* sums) {
+    return uia_seg_predict_native_ens_launch((hipStream_t)stream, K, B, S, logits, flips, threshold, src, src_bytes, desc, out, out_bytes, ws, ws_bytes, stats, sums);
+}
+
 size_t uia_mask_components_workspace_bytes(int B, int64_t pixels) { return uia_mask_components_ws_bytes(B, pixels); }
 int uia_mask_components(void* stream, int B, uint8_t* buf, size_t buf_bytes, const int32_t* desc, void* ws, size_t ws_bytes, int32_t* stats, int32_t* list, int max_list) {
     return uia_mask_components_launch((hipStream_t)stream, B, buf, buf_bytes, desc, ws, ws_bytes, stats, list, max_list);

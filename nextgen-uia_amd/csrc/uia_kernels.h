@@ -120,6 +120,10 @@ int uia_resize_batch_rgb_launch(hipStream_t stream, int B, int S, const uint8_t*
 size_t uia_seg_native_ws_bytes(int B);
 int uia_seg_predict_native_launch(hipStream_t stream, int B, int S, const float* logits, const uint8_t* src, size_t src_bytes, const int32_t* desc, uint8_t* out,
                                   size_t out_bytes, void* ws, size_t ws_bytes, int32_t* stats);
+size_t uia_seg_native_ens_ws_bytes(int B);
+int uia_seg_predict_native_ens_launch(hipStream_t stream, int K, int B, int S, const float* logits, uint32_t flips, float threshold, const uint8_t* src,
+                                      size_t src_bytes, const int32_t* desc, uint8_t* out, size_t out_bytes, void* ws, size_t ws_bytes, int32_t* stats,
+                                      uint64_t* sums);
 size_t uia_mask_components_ws_bytes(int B, int64_t pixels);
 int uia_mask_components_launch(hipStream_t stream, int B, uint8_t* buf, size_t buf_bytes, const int32_t* desc, void* ws, size_t ws_bytes, int32_t* stats, int32_t* list,
                                int max_list);

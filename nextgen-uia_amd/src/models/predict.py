@@ -1,6 +1,7 @@
 """Prediction on pictures without labels: a trained supervised entry applied to a directory of images, at each image's own size.
 
     python -m src.models.predict --entry biomedclip.segmentation --images DIR --out DIR [--checkpoint FILE] [--no-overlay] -- <that entry's own flags>
+    python -m src.models.predict ... --ensemble SEED2.pth SEED3.pth --tta flips --threshold 0.4 --prob --spread -- <that entry's own flags>
 
 --entry names a module src.models.<family>.<segmentation|classification> (ENTRIES below: the supervised entries, CLIPSeg with its per-batch prompt);
 everything else — the few-shot, fine-tune, zero-shot and retrieval modules, a module that does not exist — is refused by name before a model is built.
@@ -21,6 +22,18 @@ Segmentation only: --min_area N (components below N pixels leave the mask), --ke
 back: masks, overlays and predictions.csv then describe the filtered mask, and with --lesions K > 0
     OUT/lesions.csv            name,lesion,area,ymin,xmin,ymax,xmax,cy,cx     one row per kept component, at most K per picture, largest first, numbered
                                                                               from 1 (equal areas: the one whose first pixel comes first); none for an empty mask
+
+Ensembles: --ensemble FILE [FILE ...] names further checkpoints beside --checkpoint, each loaded into its own prepare_model instance by load_model (a
+missing file is refused before the GPU is initialised); --tta {none,hflip,vflip,flips} runs every checkpoint on the S x S model input as it is and
+flipped (torch.flip behind the task's to_input): identity; identity and horizontal; identity and vertical; identity, horizontal, vertical and both.
+Members = checkpoints x flips, checkpoint-major; more than 16 are refused by name before anything of the entry is imported.  Classification averages
+the members' softmax; its CSV header does not change.  Segmentation makes ONE launch of uia_hip.ops.seg_predict_native_ens per batch in place of the
+launch above: every member's logits are un-flipped and upsampled to the image's own size, p_k = sigmoid(u_1 - u_0), P = their mean, the mask is
+255 where P > --threshold T (default 0.5, 0 < T < 1), and
+    OUT/probs/<stem>.png       with --prob: 8-bit grey, round(255 P)          OUT/spread/<stem>.png      with --spread: 8-bit grey, round(255 (max_k p_k - min_k p_k))
+--threshold, --prob and --spread are for segmentation only.  When any of the five flags is given, predictions.csv of a segmentation entry gains two
+trailing columns, six decimals each: mean_foreground_probability = the sum of the probability bytes over the UNFILTERED mask / (255 x its pixels), empty
+for an empty mask, and mean_spread = the sum of the spread bytes / (255 x H x W).  Without them the old launch runs and the old bytes are written.
 """
 import argparse
 import importlib
@@ -41,6 +54,12 @@ SEG_HEADER = "name,width,height,foreground_pixels,foreground_fraction,ymin,xmin,
 CLS_HEADER = "name,width,height,p0,p1,predicted"
 LESION_HEADER = "name,lesion,area,ymin,xmin,ymax,xmax,cy,cx"
 MAX_LESIONS = 32
+ENS_COLUMNS = "mean_foreground_probability,mean_spread"
+MAX_MEMBERS = 16
+TTA_FLIPS = {"none": (0,), "hflip": (0, 1), "vflip": (0, 2), "flips": (0, 1, 2, 3)}      # bit 0: the input is flipped horizontally, bit 1: vertically
+ENSEMBLE_FLAGS = {"ensemble": ("--ensemble", None), "tta": ("--tta", "none"), "threshold": ("--threshold", 0.5), "prob": ("--prob", False),
+                  "spread": ("--spread", False)}
+SEG_ONLY_FLAGS = ("threshold", "prob", "spread")
 COMPONENT_FLAGS = {"min_area": ("--min_area", 0), "keep_largest": ("--keep_largest", 0), "connectivity": ("--connectivity", 8), "lesions": ("--lesions", 0)}
 
 
@@ -65,7 +84,36 @@ def get_args(argv=None):
     p.add_argument("--keep_largest", type=int, default=0, help="segmentation: only the K largest components stay (0: any number)")
     p.add_argument("--connectivity", type=int, default=8, choices=(4, 8), help="segmentation: what joins two pixels into one component")
     p.add_argument("--lesions", type=int, default=0, help=f"segmentation: write OUT/lesions.csv with the K <= {MAX_LESIONS} largest kept components of every picture")
+    p.add_argument("--ensemble", type=str, nargs="+", default=None, metavar="FILE", help="further checkpoints beside --checkpoint, averaged with it")
+    p.add_argument("--tta", type=str, default="none", choices=tuple(TTA_FLIPS), help="flips of the model input every checkpoint is run on: identity; identity "
+                   f"and horizontal; identity and vertical; all four.  Members = checkpoints x flips, at most {MAX_MEMBERS}")
+    p.add_argument("--threshold", type=float, default=0.5, help="segmentation: the mask is 255 where the mean foreground probability exceeds T, 0 < T < 1")
+    p.add_argument("--prob", default=False, action="store_true", help="segmentation: write OUT/probs/<stem>.png, the mean foreground probability as 8-bit grey")
+    p.add_argument("--spread", default=False, action="store_true", help="segmentation: write OUT/spread/<stem>.png, max - min of the members' probabilities")
     return p.parse_args(own), rest
+
+
+def ensemble_given(own):
+    """The new flags that differ from their defaults, by name: with none of them prediction runs exactly as it did before they existed."""
+    return [flag for key, (flag, default) in ENSEMBLE_FLAGS.items() if getattr(own, key) != default]
+
+
+def members_of(own):
+    """-> [(checkpoint index, flip)]: checkpoints (--checkpoint, then --ensemble in the order given) x flips of --tta, checkpoint-major."""
+    return [(c, f) for c in range(1 + len(own.ensemble or ())) for f in TTA_FLIPS[own.tta]]
+
+
+def check_ensemble(own, kind):
+    """The ensemble flags within the kernel's limits and the segmentation-only ones on a segmentation entry: refused by name before anything of the entry
+    is imported."""
+    given = [ENSEMBLE_FLAGS[key][0] for key in SEG_ONLY_FLAGS if getattr(own, key) != ENSEMBLE_FLAGS[key][1]]
+    if kind != "segmentation" and given:
+        raise ValueError(f"--entry {own.entry}: {', '.join(given)} shape segmentation masks and maps; a classification entry has none")
+    if not 0.0 < own.threshold < 1.0:
+        raise ValueError(f"--threshold {own.threshold}: 0 < T < 1")
+    n = len(members_of(own))
+    if n > MAX_MEMBERS:
+        raise ValueError(f"--ensemble / --tta: {1 + len(own.ensemble or ())} checkpoints x {len(TTA_FLIPS[own.tta])} flips = {n} members, at most {MAX_MEMBERS}")
 
 
 def check_components(own, kind):
@@ -93,12 +141,19 @@ def default_checkpoint(entry_args):
     return f"runs/{entry_args.exp}/{entry_args.dataset}/train/best_model.pth"
 
 
-def seg_csv(names, sizes, stats):
-    """names, [(H, W)], stats rows (foreground pixels, ymin, xmin, ymax, xmax, ...) -> the text of predictions.csv."""
-    lines = [SEG_HEADER]
-    for name, (H, W), s in zip(names, sizes, stats):
+def seg_csv(names, sizes, stats, sums=None, filtered=False):
+    """names, [(H, W)], stats rows (foreground pixels, ymin, xmin, ymax, xmax, ...) -> the text of predictions.csv.  With sums rows (sum of the
+    probability bytes over the launch's own mask, sum of the spread bytes) the two ensemble columns follow; `filtered` says that the stats are
+    uia_mask_components', whose word 7 is the foreground before the filter."""
+    lines = [SEG_HEADER if sums is None else f"{SEG_HEADER},{ENS_COLUMNS}"]
+    for i, (name, (H, W), s) in enumerate(zip(names, sizes, stats)):
         n, box = int(s[0]), ",".join(str(int(v)) for v in s[1:5]) if int(s[0]) > 0 else ",,,"
-        lines.append(f"{name},{W},{H},{n},{n / (H * W):.6f},{box}")
+        line = f"{name},{W},{H},{n},{n / (H * W):.6f},{box}"
+        if sums is not None:
+            before = int(s[7]) if filtered else n
+            line += f",{int(sums[i][0]) / (255 * before):.6f}" if before > 0 else ","
+            line += f",{int(sums[i][1]) / (255 * H * W):.6f}"
+        lines.append(line)
     return "\n".join(lines) + "\n"
 
 
@@ -150,6 +205,10 @@ def run(own, entry_args, module, kind):
         raise FileExistsError(f"--out {own.out} exists and is not an empty directory: nothing is overwritten")
     if not os.path.isfile(checkpoint):
         raise FileNotFoundError(f"checkpoint {checkpoint} not found (train the entry first, or pass --checkpoint)")
+    for extra in own.ensemble or ():
+        if not os.path.isfile(extra):
+            raise FileNotFoundError(f"--ensemble {extra} not found")
+    extended, members = bool(ensemble_given(own)), members_of(own)
     if hasattr(module, "check_args"):
         module.check_args(entry_args)
     dm = ImageDirModule(own.images, entry_args.img_size, entry_args.batch_size, getattr(entry_args, "num_workers", 0))
@@ -158,16 +217,17 @@ def run(own, entry_args, module, kind):
 
     torch.cuda.set_device(torch.device(entry_args.device))
     UF.set_compute_dtype(torch.bfloat16 if entry_args.dtype == "bf16" else torch.float32)
-    model = load_model(module, entry_args, checkpoint)
+    models = [load_model(module, entry_args, c) for c in [checkpoint] + list(own.ensemble or ())]
+    model = models[0]
     prompt = getattr(module, "_batch_prompt", None)              # CLIPSeg: the per-batch prompt keyword function its test() hands to the loop
     kwargs_for = prompt(entry_args) if prompt is not None else (lambda n: {})
     os.makedirs(own.out, exist_ok=True)
     writer = NativeMaskWriter(own.out, overlay=own.overlay, min_area=own.min_area, keep=own.keep_largest, connectivity=own.connectivity,
-                              lesions=own.lesions) if seg else None
+                              lesions=own.lesions, threshold=own.threshold, prob=own.prob, spread=own.spread) if seg else None
     pf = folder.RaggedPrefetcher(dm.loader, entry_args.device)
     resize = folder.ResizeStage(entry_args.img_size, with_mask=seg)
     cur = torch.cuda.current_stream()
-    seen, probs, batches, lists = 0, [], [], []
+    seen, probs, batches, lists, sums = 0, [], [], [], []
     try:
         for batch, second, ready in pf:
             cur.wait_event(ready)
@@ -176,13 +236,21 @@ def run(own, entry_args, module, kind):
             seen += n
             images, second = resize(batch, second)
             images, _ = task.to_input(images, second, entry_args.in_channels)
-            logits = model(images, **kwargs_for(n)).detach()
+            if not extended:
+                logits = model(images, **kwargs_for(n)).detach()
+                if seg:
+                    writer.submit(logits, batch, names)
+                else:
+                    probs.append(torch.softmax(logits.float(), dim=1))
+                continue
+            flipped = {f: images if f == 0 else torch.flip(images, dims=[d for d, bit in ((-1, 1), (-2, 2)) if f & bit]) for f in TTA_FLIPS[own.tta]}
+            stack = torch.stack([models[c](flipped[f], **kwargs_for(n)).detach().float() for c, f in members])
             if seg:
-                writer.submit(logits, batch, names)
+                writer.submit(stack, batch, names, flips=[f for _, f in members])
             else:
-                probs.append(torch.softmax(logits.float(), dim=1))
+                probs.append(torch.softmax(stack, dim=2).mean(dim=0))
         if seg:
-            batches, lists, writer = writer.close(), writer.lesion_lists(), None     # the writers are joined; a writer's exception surfaces here
+            batches, lists, sums, writer = writer.close(), writer.lesion_lists(), writer.sums(), None     # the writers are joined; a writer's exception surfaces here
     finally:
         if writer is not None:
             writer.close()
@@ -192,7 +260,8 @@ def run(own, entry_args, module, kind):
     if seg:
         done = [name for b in batches for name in b[0]]
         assert done == ds.names, "a batch is missing from the writers' results"
-        text = seg_csv(ds.names, sizes, [row for b in batches for row in b[2]])
+        text = seg_csv(ds.names, sizes, [row for b in batches for row in b[2]], [row for b in sums for row in b] if extended else None,
+                       filtered=(own.min_area, own.keep_largest, own.connectivity, own.lesions) != (0, 0, 8, 0))
         if own.lesions > 0:
             with open(os.path.join(own.out, "lesions.csv"), "w") as f:
                 f.write(lesions_csv(ds.names, [rows for b in lists for rows in b]))
@@ -207,6 +276,7 @@ def main(argv=None):
     own, rest = get_args(argv)
     family, kind = entry_kind(own.entry)                         # refused by name before anything of the entry is imported or built
     check_components(own, kind)
+    check_ensemble(own, kind)
     module = importlib.import_module(f"src.models.{family}.{kind}")
     entry_args = module.get_args(rest)
     out = run(own, entry_args, module, kind)

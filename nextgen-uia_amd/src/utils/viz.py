@@ -141,10 +141,24 @@ class NativeMaskWriter:
     Otherwise ONE `uia_hip.ops.mask_components` call on the device buffer follows the launch, before the copies: components below min_area pixels and
     those beyond the `keep` largest (0 = any number) leave masks and overlays, the slot's stats are that call's (words 0-4 keep their meaning, 5-7 are
     components found, kept and the foreground before), and the first `lesions` (<= 32) kept components of every image are copied into the slot as well:
-    `lesion_lists()` returns them after `close()`, int32 [n, lesions, 8] per batch in submission order."""
+    `lesion_lists()` returns them after `close()`, int32 [n, lesions, 8] per batch in submission order.
 
-    def __init__(self, out_dir, overlay=True, workers=MAX_WRITERS, level=PNG_LEVEL, device=None, min_area=0, keep=0, connectivity=8, lesions=0):
+    threshold / prob / spread, and `submit` with logits [K, n, 2, S, S] or with `flips`: the ensemble launch.  With a 4-D tensor, no flips and these three
+    at their defaults `submit` makes the `seg_predict_native` call above and nothing else.  Otherwise it makes ONE `uia_hip.ops.seg_predict_native_ens`
+    launch in its place: the mask is 255 where the members' mean foreground probability exceeds `threshold`; with prob=True `probs/<stem>.png` (8-bit grey,
+    that mean) and with spread=True `spread/<stem>.png` (8-bit grey, the largest minus the smallest member) are written too, their planes lying behind the
+    image's overlay in the buffer.  The slot then carries the launch's sums as well: `sums()` returns them after `close()`, int64 [n, 2] per batch in
+    submission order (sum of the probability bytes over the launch's own mask, sum of the spread bytes over the image).  The component filter runs behind
+    the launch as before and touches only masks and overlays."""
+
+    def __init__(self, out_dir, overlay=True, workers=MAX_WRITERS, level=PNG_LEVEL, device=None, min_area=0, keep=0, connectivity=8, lesions=0, threshold=0.5,
+                 prob=False, spread=False):
         self.out_dir, self.overlay, self.level = Path(out_dir), bool(overlay), level
+        self.threshold, self.prob, self.spread = float(threshold), bool(prob), bool(spread)
+        if not 0.0 < self.threshold < 1.0:
+            raise ValueError(f"NativeMaskWriter: threshold={threshold} (0 < threshold < 1)")
+        self.ensemble = (self.threshold, self.prob, self.spread) != (0.5, False, False)
+        self._sums = {}
         self.min_area, self.keep, self.connectivity, self.lesions = int(min_area), int(keep), int(connectivity), int(lesions)
         if self.min_area < 0 or self.keep < 0 or self.connectivity not in (4, 8) or not 0 <= self.lesions <= 32:
             raise ValueError(f"NativeMaskWriter: min_area={min_area}, keep={keep} (>= 0), connectivity={connectivity} (4 or 8), lesions={lesions} (0 .. 32)")
@@ -154,38 +168,52 @@ class NativeMaskWriter:
         (self.out_dir / "masks").mkdir(parents=True, exist_ok=True)
         if self.overlay:
             (self.out_dir / "overlays").mkdir(parents=True, exist_ok=True)
+        if self.prob:
+            (self.out_dir / "probs").mkdir(parents=True, exist_ok=True)
+        if self.spread:
+            (self.out_dir / "spread").mkdir(parents=True, exist_ok=True)
         workers = max(1, min(int(workers), MAX_WRITERS))
         self._free = queue.Queue()
         for _ in range(workers + 2):
-            self._free.put({"desc": None, "out": None, "stats": None, "cdesc": None, "list": None})
+            self._free.put({"desc": None, "out": None, "stats": None, "cdesc": None, "list": None, "sums": None})
         self._dev_out = None
         self._pool = ThreadPoolExecutor(max_workers=workers, thread_name_prefix="native-mask")
         self._jobs, self._done = [], {}
         self.files = self.bytes = self.batches = 0
 
     @staticmethod
-    def layout(sizes, overlay):
-        """[(H, W)] -> ([(mask offset, overlay offset or -1)], total bytes): every image's mask, then its overlay, back to back."""
+    def layout(sizes, overlay, prob=False, spread=False):
+        """[(H, W)] -> ([(mask offset, overlay offset or -1)], total bytes): every image's mask, then its overlay, back to back.  With prob or spread the
+        image's probability plane and then its spread plane lie behind its overlay, and the rows are (mask, overlay or -1, probability or -1, spread or
+        -1) offsets."""
         at, where = 0, []
         for H, W in sizes:
             moff, at = at, at + H * W
-            ooff = -1
+            ooff = poff = roff = -1
             if overlay:
                 ooff, at = at, at + 3 * H * W
-            where.append((moff, ooff))
+            if prob:
+                poff, at = at, at + H * W
+            if spread:
+                roff, at = at, at + H * W
+            where.append((moff, ooff, poff, roff) if prob or spread else (moff, ooff))
         return where, at
 
-    def submit(self, logits, batch, names):
+    def submit(self, logits, batch, names, flips=None):
         """logits fp32 [n, 2, S, S] on the device, batch the folder.RaggedBatch the logits were computed from (its descriptor carries every image's
-        offset, H and W), n file names.  Enqueues on the current stream and returns; the files appear behind it."""
+        offset, H and W), n file names.  Enqueues on the current stream and returns; the files appear behind it.  An ensemble: logits [K, n, 2, S, S] and
+        flips, K values 0 .. 3 (bit 0: the member saw the horizontally flipped input, bit 1: the vertically flipped one; None: no member did)."""
         from uia_hip import ops
         n = len(names)
-        if not (n > 0 and logits.shape[0] == n and batch.desc.shape[0] == n):
-            raise ValueError(f"NativeMaskWriter.submit: {n} names for {logits.shape[0]} predictions of {batch.desc.shape[0]} images")
+        members = logits.dim() == 5
+        if not (n > 0 and logits.shape[1 if members else 0] == n and batch.desc.shape[0] == n):
+            raise ValueError(f"NativeMaskWriter.submit: {n} names for {logits.shape[1 if members else 0]} predictions of {batch.desc.shape[0]} images")
+        ens = members or flips is not None or self.ensemble
         self._reap()
         geo = batch.desc[:, :3].tolist()
         sizes = [(H, W) for _, H, W in geo]
-        where, total = self.layout(sizes, self.overlay)
+        where, total = self.layout(sizes, self.overlay, self.prob, self.spread)
+        where = [(w + (-1, -1))[:4] for w in where]
         slot = self._free.get()
         if slot["desc"] is None or slot["desc"].shape[0] < n:
             slot["desc"] = torch.empty(n, ops.SEG_NATIVE_DESC, dtype=torch.int32, pin_memory=True)
@@ -195,15 +223,26 @@ class NativeMaskWriter:
         if self._dev_out is None or self._dev_out.numel() < total:
             self._dev_out = torch.empty(total + total // 4, dtype=torch.uint8, device=self.device)
         desc = slot["desc"][:n]
-        desc.copy_(torch.tensor([[off if self.overlay else -1, H, W, moff, ooff, 0, 0, 0] for (off, H, W), (moff, ooff) in zip(geo, where)], dtype=torch.int32))
         out = self._dev_out[:total]
-        stats = ops.seg_predict_native(logits.detach().float().contiguous(), batch.data if self.overlay else None, desc, out)
+        src = batch.data if self.overlay else None
+        if not ens:
+            desc.copy_(torch.tensor([[off if self.overlay else -1, H, W, moff, ooff, 0, 0, 0] for (off, H, W), (moff, ooff, _, _) in zip(geo, where)],
+                                    dtype=torch.int32))
+            stats = ops.seg_predict_native(logits.detach().float().contiguous(), src, desc, out)
+        else:
+            desc.copy_(torch.tensor([[off if self.overlay else -1, H, W, moff, ooff, poff, roff, 0] for (off, H, W), (moff, ooff, poff, roff) in zip(geo, where)],
+                                    dtype=torch.int32))
+            stack = (logits if members else logits.unsqueeze(0)).detach().float().contiguous()
+            stats, sums = ops.seg_predict_native_ens(stack, [0] * stack.shape[0] if flips is None else flips, src, desc, out, threshold=self.threshold)
+            if slot["sums"] is None or slot["sums"].shape[0] < n:
+                slot["sums"] = torch.empty(n, 2, dtype=torch.int64, pin_memory=True)
+            slot["sums"][:n].copy_(sums, non_blocking=True)
         if self.components:
             if slot["cdesc"] is None or slot["cdesc"].shape[0] < n:
                 slot["cdesc"] = torch.empty(n, ops.MASK_COMPONENTS_DESC, dtype=torch.int32, pin_memory=True)
                 slot["list"] = torch.empty(n, self.lesions, 8, dtype=torch.int32, pin_memory=True)
             cdesc = slot["cdesc"][:n]
-            cdesc.copy_(torch.tensor([[moff, H, W, ooff, self.min_area, self.keep, self.connectivity, 0] for (H, W), (moff, ooff) in zip(sizes, where)],
+            cdesc.copy_(torch.tensor([[moff, H, W, ooff, self.min_area, self.keep, self.connectivity, 0] for (H, W), (moff, ooff, _, _) in zip(sizes, where)],
                                      dtype=torch.int32))
             stats, rows = ops.mask_components(out, cdesc, self.lesions)
             slot["list"][:n].copy_(rows, non_blocking=True)
@@ -211,21 +250,25 @@ class NativeMaskWriter:
         slot["stats"][:n].copy_(stats, non_blocking=True)
         done = torch.cuda.Event()
         done.record()
-        self._jobs.append(self._pool.submit(self._write, self.batches, done, slot, list(names), sizes, where))
+        self._jobs.append(self._pool.submit(self._write, self.batches, done, slot, list(names), sizes, where, ens))
         self.batches += 1
 
-    def _write(self, k, done, slot, names, sizes, where):
+    def _write(self, k, done, slot, names, sizes, where, ens=False):
         try:
             done.synchronize()
-            flat, size = slot["out"].numpy(), 0
-            for name, (H, W), (moff, ooff) in zip(names, sizes, where):
+            flat, size, files = slot["out"].numpy(), 0, 0
+            for name, (H, W), (moff, ooff, poff, roff) in zip(names, sizes, where):
                 stem = str(Path(name).stem)
-                size += write_png(self.out_dir / "masks" / f"{stem}.png", flat[moff:moff + H * W].reshape(H, W), self.level)
-                if ooff >= 0:
-                    size += write_png(self.out_dir / "overlays" / f"{stem}.png", flat[ooff:ooff + 3 * H * W].reshape(H, W, 3), self.level)
+                planes = [("masks", moff, (H, W)), ("overlays", ooff, (H, W, 3)), ("probs", poff, (H, W)), ("spread", roff, (H, W))]
+                for folder, off, shape in planes:
+                    if off >= 0:
+                        size += write_png(self.out_dir / folder / f"{stem}.png", flat[off:off + int(np.prod(shape))].reshape(shape), self.level)
+                        files += 1
             if self.components:
                 self._lists[k] = slot["list"][:len(names)].clone().numpy()
-            return k, names, sizes, slot["stats"][:len(names)].clone().numpy(), (2 if self.overlay else 1) * len(names), size
+            if ens:
+                self._sums[k] = slot["sums"][:len(names)].clone().numpy()
+            return k, names, sizes, slot["stats"][:len(names)].clone().numpy(), files, size
         finally:
             self._free.put(slot)
 
@@ -254,3 +297,8 @@ class NativeMaskWriter:
         """After close(): per batch, in submission order, int32 [n, lesions, 8] — per image the first `lesions` kept components, largest first, as rows
         (area, ymin, xmin, ymax, xmax, first pixel, cy, cx), unused rows zero.  Empty when the writer filters nothing."""
         return [self._lists[k] for k in sorted(self._lists)]
+
+    def sums(self):
+        """After close(): per batch that went through the ensemble launch, in submission order, int64 [n, 2] — per image the sum of the probability bytes
+        over the launch's own (unfiltered) mask and the sum of the spread bytes over the image.  Empty when no batch did."""
+        return [self._sums[k] for k in sorted(self._sums)]

@@ -175,6 +175,8 @@ PROTOTYPES = {
     "uia_resize_batch_rgb": (C.c_int, [vp, C.c_int, C.c_int, vp, sz, vp, vp, sz, vp]),
     "uia_seg_native_workspace_bytes": (sz, [C.c_int]),
     "uia_seg_predict_native": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, sz, vp, vp, sz, vp, sz, vp]),
+    "uia_seg_native_ens_workspace_bytes": (sz, [C.c_int]),
+    "uia_seg_predict_native_ens": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_uint32, f32, vp, sz, vp, vp, sz, vp, sz, vp, vp]),
     "uia_mask_components_workspace_bytes": (sz, [C.c_int, C.c_int64]),
     "uia_mask_components": (C.c_int, [vp, C.c_int, vp, sz, vp, vp, sz, vp, vp, C.c_int]),
     "uia_infonce_workspace_bytes": (sz, [C.c_int, C.c_int]),

@@ -2061,6 +2061,74 @@ def seg_predict_native(logits, src, desc, out, stats=None):
     return stats
 
 
+# ---------------------------------------------------------------- the same for an ensemble of K members (csrc/seg_native_ens.hip)
+SEG_NATIVE_ENS_MAX_K = 16
+_SEG_NATIVE_ENS_WS = {}
+
+
+def seg_native_ens_workspace(B, device):
+    """The scratch of uia_seg_predict_native_ens on B images, kept per (device, stream, B): launches of one stream are ordered, so they may share it."""
+    need = lib().uia_seg_native_ens_workspace_bytes(int(B))
+    if need == 0:
+        raise UiaError(f"seg_predict_native_ens: B={B} is outside the kernel's limits (1 <= B <= 65535)")
+    key = (device.index if device.index is not None else torch.cuda.current_device(), torch.cuda.current_stream(device).cuda_stream, int(B))
+    ws = _SEG_NATIVE_ENS_WS.get(key)
+    if ws is None:
+        ws = _SEG_NATIVE_ENS_WS[key] = torch.empty(need, device=device, dtype=torch.uint8)
+    return ws
+
+
+def seg_flip_bits(flips):
+    """A sequence of K values 0 .. 3 (1: the member saw the horizontally flipped input, 2: the vertically flipped one, 3: both) -> the `flips` word of
+    uia_seg_predict_native_ens, two bits per member."""
+    flips = [int(f) for f in flips]
+    if not 1 <= len(flips) <= SEG_NATIVE_ENS_MAX_K or any(f not in (0, 1, 2, 3) for f in flips):
+        raise UiaError(f"seg_predict_native_ens: flips must be 1 .. {SEG_NATIVE_ENS_MAX_K} values 0 .. 3, one per member, got {flips}")
+    word = 0
+    for k, f in enumerate(flips):
+        word |= f << (2 * k)
+    return word
+
+
+def seg_predict_native_ens(logits, flips, src, desc, out, threshold=0.5, stats=None, sums=None):
+    """seg_predict_native for K members: logits fp32 [K, B, 2, S, S] on the device, flips a sequence of K values 0 .. 3 (bit 0: member k's logits are of
+    the horizontally flipped S x S input, bit 1: of the vertically flipped one; the kernel un-flips while it reads); src and out as seg_predict_native's;
+    desc a HOST int32 tensor [B, 8], per image (source offset or -1, H, W, mask offset, overlay offset or -1, probability offset or -1, spread offset or -1,
+    0) -> (stats int32 [B, 8], sums int64 [B, 2]) on the device.  One launch writes every image's mask (255 where the members' mean foreground
+    probability P > threshold), its overlay, q = (uint8)(255 P + 0.5) at the probability offset and r = (uint8)(255 (max_k p_k - min_k p_k) + 0.5) at the
+    spread offset; sums = (sum of q over the mask, sum of r over the image).  A pixel with a NaN member: mask 0, q 0, r 255.  Enqueued only."""
+    _p(logits), _p(src), _p(out), _p(stats), _p(sums)
+    if logits.dim() != 5 or logits.shape[2] != 2 or logits.shape[3] != logits.shape[4] or logits.dtype != torch.float32 or not logits.is_contiguous():
+        raise UiaError(f"seg_predict_native_ens: logits must be contiguous fp32 [K, B, 2, S, S], got {logits.dtype} {tuple(logits.shape)}")
+    K, B, _, S, _ = logits.shape
+    flips = list(flips)
+    word = seg_flip_bits(flips)
+    if len(flips) != K:
+        raise UiaError(f"seg_predict_native_ens: {len(flips)} flips for {K} members")
+    threshold = float(threshold)
+    if not 0.0 < threshold < 1.0:
+        raise UiaError(f"seg_predict_native_ens: threshold {threshold} (0 < threshold < 1)")
+    for t, name in ((src, "src"), (out, "out")):
+        if t is not None and (t.dim() != 1 or t.dtype != torch.uint8 or not t.is_contiguous() or t.device != logits.device):
+            raise UiaError(f"seg_predict_native_ens: {name} must be a contiguous 1-D uint8 tensor on the logits' device, got {t.dtype} {tuple(t.shape)}")
+    if out is None:
+        raise UiaError("seg_predict_native_ens: out is required (the caller lays the masks, overlays and maps out in it)")
+    if (not isinstance(desc, torch.Tensor) or desc.is_cuda or desc.dtype != torch.int32 or tuple(desc.shape) != (B, SEG_NATIVE_DESC) or not desc.is_contiguous()):
+        raise UiaError(f"seg_predict_native_ens: desc must be a contiguous host int32 tensor [{B}, {SEG_NATIVE_DESC}]")
+    if stats is None:
+        stats = torch.empty((B, SEG_NATIVE_DESC), dtype=torch.int32, device=logits.device)
+    if tuple(stats.shape) != (B, SEG_NATIVE_DESC) or stats.dtype != torch.int32 or not stats.is_contiguous() or stats.device != logits.device:
+        raise UiaError(f"seg_predict_native_ens: stats must be contiguous int32 [{B}, {SEG_NATIVE_DESC}] on the logits' device")
+    if sums is None:
+        sums = torch.empty((B, 2), dtype=torch.int64, device=logits.device)
+    if tuple(sums.shape) != (B, 2) or sums.dtype != torch.int64 or not sums.is_contiguous() or sums.device != logits.device:
+        raise UiaError(f"seg_predict_native_ens: sums must be contiguous int64 [{B}, 2] on the logits' device")
+    ws = seg_native_ens_workspace(B, logits.device)
+    check(lib().uia_seg_predict_native_ens(_stream(), K, B, S, _p(logits), word, threshold, _p(src), 0 if src is None else src.numel(), desc.data_ptr(), _p(out),
+                                           out.numel(), _p(ws), ws.numel(), _p(stats), _p(sums)), "uia_seg_predict_native_ens")
+    return stats, sums
+
+
 # ---------------------------------------------------------------- connected components of native-size masks (csrc/components.hip)
 MASK_COMPONENTS_DESC = 8                   # int32 per image: mask offset, H, W, overlay offset or -1, min_area, keep, connectivity (4 | 8), 0
 MASK_COMPONENTS_MAX_LIST = 32
