@@ -684,6 +684,29 @@ size_t uia_mask_components_workspace_bytes(int B, int64_t pixels);
 int uia_mask_components(void* stream, int B, uint8_t* buf, size_t buf_bytes, const int32_t* desc, void* ws, size_t ws_bytes, int32_t* stats, int32_t* list,
                         int max_list);
 
+/* Disk closing, hole filling and disk opening of native-size masks where they lie (csrc/morphology.hip).  buf: one DEVICE byte buffer of buf_bytes bytes
+ * (< 2^31), in the prediction path the `out` buffer of uia_seg_predict_native / _ens as it returned.  desc: a HOST array int32 [B][8], per image
+ * (mask_offset, H, W, overlay_offset or -1, r_close, r_open, hole_area, hole_connectivity); offsets are arbitrary bytes.  A mask byte != 0 is
+ * foreground.  With D the image's pixel grid and disk(r) = {(dy, dx) : dy^2 + dx^2 <= r^2}:  dilate_r(X) = {p in D : some q in X with p - q in disk(r)}
+ * (the exact squared Euclidean distance from p to X is <= r^2; pixels outside the image contribute nothing);  erode_r(X) = D \ dilate_r(D \ X) (only
+ * background INSIDE the image erodes: scipy's binary_dilation(border_value=0) / binary_erosion(border_value=1) with the disk, so closing is extensive,
+ * opening anti-extensive, both idempotent);  a hole is a connected component of the background under hole_connectivity (4 or 8) with no pixel in the
+ * first or last row or column of the image; it is filled when hole_area == -1 (any size) or its area <= hole_area; hole_area == 0 fills nothing.
+ * Per image, in this order: X1 = erode_rc(dilate_rc(X0)), X2 = X1 + the filled holes of X1, X3 = dilate_ro(erode_ro(X2)); a radius of 0 is the identity.
+ * Written: a pixel of X3 \ X0 gets mask byte 255 and, with an overlay, overlay byte[1] = 255; a pixel of X0 \ X3 gets mask byte 0 and overlay byte[1] =
+ * byte[0]; every other byte keeps its value, bytes other than 255 included.  stats: DEVICE int32 [B][8] = (foreground after, ymin, xmin, ymax, xmax after,
+ * pixels added, pixels removed, foreground before), the box of an empty result (INT_MAX, INT_MAX, -1, -1): words 0-4 mean what they mean in
+ * uia_seg_predict_native.  Every word of stats is written; nothing beside stats, the mask bytes and the overlays' green bytes is touched.
+ * Checked before anything is enqueued (non-zero, nothing written, the image's index in uia_last_error()): 1 <= B <= 65535, 1 <= H, W <= 16384, null
+ * buf / desc / ws / stats, a radius outside 0 .. 64, a hole_area below -1, a hole_connectivity other than 4 or 8 (even where hole_area is 0), an offset
+ * below -1 or a mask offset of -1, a mask or overlay that leaves buf, ranges that overlap each other, stats or the workspace, a workspace below
+ * uia_mask_morphology_workspace_bytes(B, pixels) with pixels = the sum of H * W over the batch (0 for arguments outside the limits; 8-byte aligned;
+ * 10 bytes per pixel — two byte planes, a label and an area word — and about 40 bytes per image).  The descriptor is then copied to the workspace with
+ * hipMemcpyAsync on `stream`, so a pinned descriptor must stay as it is until that copy has run.  Only the launches some image needs are enqueued.
+ * Asynchronous, no host synchronisation; integer atomics only, so two calls on equal input give identical bytes whatever the scheduling. */
+size_t uia_mask_morphology_workspace_bytes(int B, int64_t pixels);
+int uia_mask_morphology(void* stream, int B, uint8_t* buf, size_t buf_bytes, const int32_t* desc, void* ws, size_t ws_bytes, int32_t* stats);
+
 /* ---------------------------------------------------------------------------------------------
  * Layout helpers around the GEMMs. */
 int uia_cast(void* stream, int dtype, size_t n, const float* src, void* dst, float scale);          /* dst = T(scale*src) */

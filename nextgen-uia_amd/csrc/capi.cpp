@@ -308,6 +308,11 @@ int uia_mask_components(void* stream, int B, uint8_t* buf, size_t buf_bytes, con
     return uia_mask_components_launch((hipStream_t)stream, B, buf, buf_bytes, desc, ws, ws_bytes, stats, list, max_list);
 }
 
+size_t uia_mask_morphology_workspace_bytes(int B, int64_t pixels) { return uia_mask_morphology_ws_bytes(B, pixels); }
+int uia_mask_morphology(void* stream, int B, uint8_t* buf, size_t buf_bytes, const int32_t* desc, void* ws, size_t ws_bytes, int32_t* stats) {
+    return uia_mask_morphology_launch((hipStream_t)stream, B, buf, buf_bytes, desc, ws, ws_bytes, stats);
+}
+
 int uia_im2col_padded(void* stream, int dtype, int B, int C, int H, int W, int P, const float* img, void* cols, int64_t ldo) {
     return uia_im2col_padded_launch((hipStream_t)stream, dtype, B, C, H, W, P, img, cols, (long)ldo);
 }

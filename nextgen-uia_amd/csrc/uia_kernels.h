@@ -127,6 +127,8 @@ int uia_seg_predict_native_ens_launch(hipStream_t stream, int K, int B, int S, c
 size_t uia_mask_components_ws_bytes(int B, int64_t pixels);
 int uia_mask_components_launch(hipStream_t stream, int B, uint8_t* buf, size_t buf_bytes, const int32_t* desc, void* ws, size_t ws_bytes, int32_t* stats, int32_t* list,
                                int max_list);
+size_t uia_mask_morphology_ws_bytes(int B, int64_t pixels);
+int uia_mask_morphology_launch(hipStream_t stream, int B, uint8_t* buf, size_t buf_bytes, const int32_t* desc, void* ws, size_t ws_bytes, int32_t* stats);
 int uia_im2col_padded_launch(hipStream_t stream, int dtype, int B, int C, int H, int W, int P, const float* img, void* out, long ldo);
 int uia_embed_bwd_launch(hipStream_t stream, int rows, int D, int vocab, const int64_t* ids, const float* dx, float* dtable, long pad_id);
 int uia_embed_packed_launch(hipStream_t stream, int rows, int D, int vocab, int max_pos, const int64_t* ids, const int64_t* pos_idx, const float* table, const float* pos, const float* type0, float* out);

@@ -23,6 +23,11 @@ back: masks, overlays and predictions.csv then describe the filtered mask, and w
     OUT/lesions.csv            name,lesion,area,ymin,xmin,ymax,xmax,cy,cx     one row per kept component, at most K per picture, largest first, numbered
                                                                               from 1 (equal areas: the one whose first pixel comes first); none for an empty mask
 
+--close_radius R, --open_radius R (0 .. 64) and --fill_holes N (0 off, -1 any size, N > 0 holes of at most N pixels) reshape the masks on the device
+first (uia_hip.ops.mask_morphology, one call per batch between the mask launch and the component call): a closing with the disk of radius R, the holes
+of the result filled, then an opening; a hole's connectivity is the complement of --connectivity (12 - it).  Masks, overlays, predictions.csv and
+lesions.csv then describe the reshaped mask, and predictions.csv gains the trailing columns pixels_added,pixels_removed.  Segmentation only.
+
 Ensembles: --ensemble FILE [FILE ...] names further checkpoints beside --checkpoint, each loaded into its own prepare_model instance by load_model (a
 missing file is refused before the GPU is initialised); --tta {none,hflip,vflip,flips} runs every checkpoint on the S x S model input as it is and
 flipped (torch.flip behind the task's to_input): identity; identity and horizontal; identity and vertical; identity, horizontal, vertical and both.
@@ -60,6 +65,9 @@ TTA_FLIPS = {"none": (0,), "hflip": (0, 1), "vflip": (0, 2), "flips": (0, 1, 2, 
 ENSEMBLE_FLAGS = {"ensemble": ("--ensemble", None), "tta": ("--tta", "none"), "threshold": ("--threshold", 0.5), "prob": ("--prob", False),
                   "spread": ("--spread", False)}
 SEG_ONLY_FLAGS = ("threshold", "prob", "spread")
+MORPH_COLUMNS = "pixels_added,pixels_removed"
+MAX_RADIUS = 64
+MORPHOLOGY_FLAGS = {"close_radius": ("--close_radius", 0), "open_radius": ("--open_radius", 0), "fill_holes": ("--fill_holes", 0)}
 COMPONENT_FLAGS = {"min_area": ("--min_area", 0), "keep_largest": ("--keep_largest", 0), "connectivity": ("--connectivity", 8), "lesions": ("--lesions", 0)}
 
 
@@ -84,6 +92,9 @@ def get_args(argv=None):
     p.add_argument("--keep_largest", type=int, default=0, help="segmentation: only the K largest components stay (0: any number)")
     p.add_argument("--connectivity", type=int, default=8, choices=(4, 8), help="segmentation: what joins two pixels into one component")
     p.add_argument("--lesions", type=int, default=0, help=f"segmentation: write OUT/lesions.csv with the K <= {MAX_LESIONS} largest kept components of every picture")
+    p.add_argument("--close_radius", type=int, default=0, help=f"segmentation: close the mask with a disk of radius R (0 .. {MAX_RADIUS}; 0: off)")
+    p.add_argument("--open_radius", type=int, default=0, help=f"segmentation: open the mask with a disk of radius R (0 .. {MAX_RADIUS}; 0: off), after closing and filling")
+    p.add_argument("--fill_holes", type=int, default=0, help="segmentation: fill the holes of the closed mask (0: off, -1: any size, N > 0: holes of at most N pixels)")
     p.add_argument("--ensemble", type=str, nargs="+", default=None, metavar="FILE", help="further checkpoints beside --checkpoint, averaged with it")
     p.add_argument("--tta", type=str, default="none", choices=tuple(TTA_FLIPS), help="flips of the model input every checkpoint is run on: identity; identity "
                    f"and horizontal; identity and vertical; all four.  Members = checkpoints x flips, at most {MAX_MEMBERS}")
@@ -127,6 +138,23 @@ def check_components(own, kind):
         raise ValueError(f"--lesions {own.lesions}: 0 .. {MAX_LESIONS}")
 
 
+def morphology_given(own):
+    """The morphology flags that differ from their defaults, by name: with none of them nothing else is enqueued and predictions.csv keeps its columns."""
+    return [flag for key, (flag, default) in MORPHOLOGY_FLAGS.items() if getattr(own, key) != default]
+
+
+def check_morphology(own, kind):
+    """The morphology flags are for segmentation and within the kernel's limits: refused by name before anything of the entry is imported."""
+    given = morphology_given(own)
+    if kind != "segmentation" and given:
+        raise ValueError(f"--entry {own.entry}: {', '.join(given)} reshape segmentation masks; a classification entry has none")
+    for key in ("close_radius", "open_radius"):
+        if not 0 <= getattr(own, key) <= MAX_RADIUS:
+            raise ValueError(f"--{key} {getattr(own, key)}: 0 .. {MAX_RADIUS}")
+    if own.fill_holes < -1:
+        raise ValueError(f"--fill_holes {own.fill_holes}: 0 (off), -1 (any size) or the largest hole filled, in pixels")
+
+
 def entry_kind(name):
     """"<family>.<kind>" -> (family, kind), or the refusal, by name."""
     family, _, kind = str(name).partition(".")
@@ -141,18 +169,22 @@ def default_checkpoint(entry_args):
     return f"runs/{entry_args.exp}/{entry_args.dataset}/train/best_model.pth"
 
 
-def seg_csv(names, sizes, stats, sums=None, filtered=False):
+def seg_csv(names, sizes, stats, sums=None, filtered=False, morphology=None):
     """names, [(H, W)], stats rows (foreground pixels, ymin, xmin, ymax, xmax, ...) -> the text of predictions.csv.  With sums rows (sum of the
     probability bytes over the launch's own mask, sum of the spread bytes) the two ensemble columns follow; `filtered` says that the stats are
-    uia_mask_components', whose word 7 is the foreground before the filter."""
-    lines = [SEG_HEADER if sums is None else f"{SEG_HEADER},{ENS_COLUMNS}"]
+    uia_mask_components', whose word 7 is the foreground before the filter.  With morphology rows (pixels added, pixels removed, foreground of the
+    launch's own mask: uia_mask_morphology's words 5-7) the two morphology columns come last, and the ensemble column's denominator is those rows'
+    third word: behind a morphology call the component filter's word 7 counts the morphology's result, not the launch's mask."""
+    lines = [",".join([SEG_HEADER] + ([ENS_COLUMNS] if sums is not None else []) + ([MORPH_COLUMNS] if morphology is not None else []))]
     for i, (name, (H, W), s) in enumerate(zip(names, sizes, stats)):
         n, box = int(s[0]), ",".join(str(int(v)) for v in s[1:5]) if int(s[0]) > 0 else ",,,"
         line = f"{name},{W},{H},{n},{n / (H * W):.6f},{box}"
         if sums is not None:
-            before = int(s[7]) if filtered else n
+            before = int(morphology[i][2]) if morphology is not None else (int(s[7]) if filtered else n)
             line += f",{int(sums[i][0]) / (255 * before):.6f}" if before > 0 else ","
             line += f",{int(sums[i][1]) / (255 * H * W):.6f}"
+        if morphology is not None:
+            line += f",{int(morphology[i][0])},{int(morphology[i][1])}"
         lines.append(line)
     return "\n".join(lines) + "\n"
 
@@ -223,11 +255,12 @@ def run(own, entry_args, module, kind):
     kwargs_for = prompt(entry_args) if prompt is not None else (lambda n: {})
     os.makedirs(own.out, exist_ok=True)
     writer = NativeMaskWriter(own.out, overlay=own.overlay, min_area=own.min_area, keep=own.keep_largest, connectivity=own.connectivity,
-                              lesions=own.lesions, threshold=own.threshold, prob=own.prob, spread=own.spread) if seg else None
+                              lesions=own.lesions, threshold=own.threshold, prob=own.prob, spread=own.spread, close_radius=own.close_radius,
+                              open_radius=own.open_radius, fill_holes=own.fill_holes) if seg else None
     pf = folder.RaggedPrefetcher(dm.loader, entry_args.device)
     resize = folder.ResizeStage(entry_args.img_size, with_mask=seg)
     cur = torch.cuda.current_stream()
-    seen, probs, batches, lists, sums = 0, [], [], [], []
+    seen, probs, batches, lists, sums, morph = 0, [], [], [], [], []
     try:
         for batch, second, ready in pf:
             cur.wait_event(ready)
@@ -250,7 +283,7 @@ def run(own, entry_args, module, kind):
             else:
                 probs.append(torch.softmax(stack, dim=2).mean(dim=0))
         if seg:
-            batches, lists, sums, writer = writer.close(), writer.lesion_lists(), writer.sums(), None     # the writers are joined; a writer's exception surfaces here
+            batches, lists, sums, morph, writer = writer.close(), writer.lesion_lists(), writer.sums(), writer.morphology_stats(), None     # the writers are joined; a writer's exception surfaces here
     finally:
         if writer is not None:
             writer.close()
@@ -261,7 +294,8 @@ def run(own, entry_args, module, kind):
         done = [name for b in batches for name in b[0]]
         assert done == ds.names, "a batch is missing from the writers' results"
         text = seg_csv(ds.names, sizes, [row for b in batches for row in b[2]], [row for b in sums for row in b] if extended else None,
-                       filtered=(own.min_area, own.keep_largest, own.connectivity, own.lesions) != (0, 0, 8, 0))
+                       filtered=(own.min_area, own.keep_largest, own.connectivity, own.lesions) != (0, 0, 8, 0),
+                       morphology=[row for b in morph for row in b] if morphology_given(own) else None)
         if own.lesions > 0:
             with open(os.path.join(own.out, "lesions.csv"), "w") as f:
                 f.write(lesions_csv(ds.names, [rows for b in lists for rows in b]))
@@ -276,6 +310,7 @@ def main(argv=None):
     own, rest = get_args(argv)
     family, kind = entry_kind(own.entry)                         # refused by name before anything of the entry is imported or built
     check_components(own, kind)
+    check_morphology(own, kind)
     check_ensemble(own, kind)
     module = importlib.import_module(f"src.models.{family}.{kind}")
     entry_args = module.get_args(rest)

@@ -149,10 +149,17 @@ class NativeMaskWriter:
     that mean) and with spread=True `spread/<stem>.png` (8-bit grey, the largest minus the smallest member) are written too, their planes lying behind the
     image's overlay in the buffer.  The slot then carries the launch's sums as well: `sums()` returns them after `close()`, int64 [n, 2] per batch in
     submission order (sum of the probability bytes over the launch's own mask, sum of the spread bytes over the image).  The component filter runs behind
-    the launch as before and touches only masks and overlays."""
+    the launch as before and touches only masks and overlays.
+
+    close_radius / open_radius / fill_holes: morphology on the device.  With all three at 0 nothing else is enqueued.  Otherwise ONE
+    `uia_hip.ops.mask_morphology` call on the device buffer follows the mask launch (plain or ensemble), before the optional component call and before
+    the copies: a closing with the disk of close_radius (0 .. 64), the holes of the result filled (fill_holes -1: every hole, N > 0: holes of at most N
+    pixels; a hole is a background component under the connectivity 12 - `connectivity`, the complement of the foreground's), then an opening with the
+    disk of open_radius.  The slot then carries the call's words 5-7 as well: `morphology_stats()` returns them after `close()`, int32 [n, 3] per batch
+    in submission order (pixels added, pixels removed, foreground of the launch's own mask)."""
 
     def __init__(self, out_dir, overlay=True, workers=MAX_WRITERS, level=PNG_LEVEL, device=None, min_area=0, keep=0, connectivity=8, lesions=0, threshold=0.5,
-                 prob=False, spread=False):
+                 prob=False, spread=False, close_radius=0, open_radius=0, fill_holes=0):
         self.out_dir, self.overlay, self.level = Path(out_dir), bool(overlay), level
         self.threshold, self.prob, self.spread = float(threshold), bool(prob), bool(spread)
         if not 0.0 < self.threshold < 1.0:
@@ -164,6 +171,11 @@ class NativeMaskWriter:
             raise ValueError(f"NativeMaskWriter: min_area={min_area}, keep={keep} (>= 0), connectivity={connectivity} (4 or 8), lesions={lesions} (0 .. 32)")
         self.components = (self.min_area, self.keep, self.connectivity, self.lesions) != (0, 0, 8, 0)
         self._lists = {}
+        self.close_radius, self.open_radius, self.fill_holes = int(close_radius), int(open_radius), int(fill_holes)
+        if not 0 <= self.close_radius <= 64 or not 0 <= self.open_radius <= 64 or self.fill_holes < -1:
+            raise ValueError(f"NativeMaskWriter: close_radius={close_radius}, open_radius={open_radius} (0 .. 64), fill_holes={fill_holes} (>= -1)")
+        self.morphology = (self.close_radius, self.open_radius, self.fill_holes) != (0, 0, 0)
+        self._morph = {}
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         (self.out_dir / "masks").mkdir(parents=True, exist_ok=True)
         if self.overlay:
@@ -175,7 +187,7 @@ class NativeMaskWriter:
         workers = max(1, min(int(workers), MAX_WRITERS))
         self._free = queue.Queue()
         for _ in range(workers + 2):
-            self._free.put({"desc": None, "out": None, "stats": None, "cdesc": None, "list": None, "sums": None})
+            self._free.put({"desc": None, "out": None, "stats": None, "cdesc": None, "list": None, "sums": None, "mdesc": None, "morph": None})
         self._dev_out = None
         self._pool = ThreadPoolExecutor(max_workers=workers, thread_name_prefix="native-mask")
         self._jobs, self._done = [], {}
@@ -237,6 +249,15 @@ class NativeMaskWriter:
             if slot["sums"] is None or slot["sums"].shape[0] < n:
                 slot["sums"] = torch.empty(n, 2, dtype=torch.int64, pin_memory=True)
             slot["sums"][:n].copy_(sums, non_blocking=True)
+        if self.morphology:
+            if slot["mdesc"] is None or slot["mdesc"].shape[0] < n:
+                slot["mdesc"] = torch.empty(n, ops.MASK_MORPHOLOGY_DESC, dtype=torch.int32, pin_memory=True)
+                slot["morph"] = torch.empty(n, 3, dtype=torch.int32, pin_memory=True)
+            mdesc = slot["mdesc"][:n]
+            mdesc.copy_(torch.tensor([[moff, H, W, ooff, self.close_radius, self.open_radius, self.fill_holes, 12 - self.connectivity]
+                                      for (H, W), (moff, ooff, _, _) in zip(sizes, where)], dtype=torch.int32))
+            stats = ops.mask_morphology(out, mdesc)
+            slot["morph"][:n].copy_(stats[:, 5:8], non_blocking=True)
         if self.components:
             if slot["cdesc"] is None or slot["cdesc"].shape[0] < n:
                 slot["cdesc"] = torch.empty(n, ops.MASK_COMPONENTS_DESC, dtype=torch.int32, pin_memory=True)
@@ -268,6 +289,8 @@ class NativeMaskWriter:
                 self._lists[k] = slot["list"][:len(names)].clone().numpy()
             if ens:
                 self._sums[k] = slot["sums"][:len(names)].clone().numpy()
+            if self.morphology:
+                self._morph[k] = slot["morph"][:len(names)].clone().numpy()
             return k, names, sizes, slot["stats"][:len(names)].clone().numpy(), files, size
         finally:
             self._free.put(slot)
@@ -302,3 +325,8 @@ class NativeMaskWriter:
         """After close(): per batch that went through the ensemble launch, in submission order, int64 [n, 2] — per image the sum of the probability bytes
         over the launch's own (unfiltered) mask and the sum of the spread bytes over the image.  Empty when no batch did."""
         return [self._sums[k] for k in sorted(self._sums)]
+
+    def morphology_stats(self):
+        """After close(): per batch, in submission order, int32 [n, 3] — per image (pixels the morphology added, pixels it removed, foreground of the
+        launch's own mask before it).  Empty when the writer was built without close_radius, open_radius and fill_holes."""
+        return [self._morph[k] for k in sorted(self._morph)]

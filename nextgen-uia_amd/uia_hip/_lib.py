@@ -179,6 +179,8 @@ PROTOTYPES = {
     "uia_seg_predict_native_ens": (C.c_int, [vp, C.c_int, C.c_int, C.c_int, vp, C.c_uint32, f32, vp, sz, vp, vp, sz, vp, sz, vp, vp]),
     "uia_mask_components_workspace_bytes": (sz, [C.c_int, C.c_int64]),
     "uia_mask_components": (C.c_int, [vp, C.c_int, vp, sz, vp, vp, sz, vp, vp, C.c_int]),
+    "uia_mask_morphology_workspace_bytes": (sz, [C.c_int, C.c_int64]),
+    "uia_mask_morphology": (C.c_int, [vp, C.c_int, vp, sz, vp, vp, sz, vp]),
     "uia_infonce_workspace_bytes": (sz, [C.c_int, C.c_int]),
     "uia_infonce_fwd_bwd": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, f32, f32, vp, vp, vp, vp, sz]),
     "uia_adamw_clip_step": (C.c_int, [vp, sz, vp, vp, vp, vp, f32, f32, f32, f32, f32, f32, C.c_int, f32, vp]),

@@ -2174,6 +2174,45 @@ def mask_components(buf, desc, max_list=0):
     return stats, rows
 
 
+# ---------------------------------------------------------------- disk closing / opening and hole filling of native-size masks (csrc/morphology.hip)
+MASK_MORPHOLOGY_DESC = 8                   # int32 per image: mask offset, H, W, overlay offset or -1, r_close, r_open, hole_area, hole_connectivity (4 | 8)
+MORPHOLOGY_MAX_RADIUS = 64
+_MASK_MORPHOLOGY_WS = {}
+
+
+def mask_morphology_workspace(B, pixels, device):
+    """The scratch of uia_mask_morphology on B images of `pixels` pixels in all (10 bytes per pixel), kept per (device, stream) and grown when a batch
+    needs more: launches of one stream are ordered, so they may share it."""
+    need = lib().uia_mask_morphology_workspace_bytes(int(B), int(pixels))
+    _require(need != 0, f"mask_morphology: B={B}, pixels={pixels} is outside the kernel's limits (1 <= B <= 65535, 1 <= pixels < 2^31)")
+    key = (device.index if device.index is not None else torch.cuda.current_device(), torch.cuda.current_stream(device).cuda_stream)
+    ws = _MASK_MORPHOLOGY_WS.get(key)
+    if ws is None or ws.numel() < need:
+        ws = _MASK_MORPHOLOGY_WS[key] = torch.empty(need + need // 4, device=device, dtype=torch.uint8)
+    return ws
+
+
+def mask_morphology(buf, desc):
+    """buf a 1-D uint8 device buffer holding the batch's masks (and overlays), e.g. the `out` of seg_predict_native; desc a HOST int32 tensor [B, 8], per
+    image (mask offset, H, W, overlay offset or -1, r_close, r_open, hole_area, hole_connectivity) (pinned memory makes its copy asynchronous, and it
+    must then stay unchanged until the copy has run) -> stats int32 [B, 8] on the device.  In place, per image: a closing with the disk of radius r_close
+    (0 .. 64), then the holes of the result filled (hole_area -1: every hole, N > 0: holes of at most N pixels, 0: none; a hole is a 4- / 8-connected
+    component of the background that does not touch the image's frame), then an opening with the disk of radius r_open; only background inside the
+    image erodes.  A new foreground pixel gets mask byte 255 and overlay green 255, a removed one 0 and green = red; every other byte stays.
+    stats = (foreground after, ymin, xmin, ymax, xmax, pixels added, pixels removed, foreground before).  Enqueued only."""
+    _require(isinstance(buf, torch.Tensor) and buf.is_cuda and buf.dim() == 1, "mask_morphology: buf must be a contiguous 1-D uint8 tensor on the device")
+    _dense(buf, "mask_morphology: buf", (torch.uint8,))
+    _require(isinstance(desc, torch.Tensor) and not desc.is_cuda and desc.dim() == 2 and desc.shape[1] == MASK_MORPHOLOGY_DESC and desc.shape[0] >= 1,
+             f"mask_morphology: desc must be a contiguous host int32 tensor [B, {MASK_MORPHOLOGY_DESC}]")
+    _dense(desc, "mask_morphology: desc", (torch.int32,))
+    B = desc.shape[0]
+    pixels = int((desc[:, 1].long().clamp(min=0) * desc[:, 2].long().clamp(min=0)).sum())
+    stats = torch.empty((B, 8), dtype=torch.int32, device=buf.device)
+    ws = mask_morphology_workspace(B, max(1, min(pixels, 2 ** 31 - 1)), buf.device)     # (a descriptor outside the limits is refused by the launcher, by image)
+    check(lib().uia_mask_morphology(_stream(), B, _p(buf), buf.numel(), desc.data_ptr(), _p(ws), ws.numel(), _p(stats)), "uia_mask_morphology")
+    return stats
+
+
 # ---------------------------------------------------------------- DINOv2 UNet decoder (csrc/unet_conv.hip, unet_bn.hip, unet_resample.hip)
 CONV3, CONVT_FWD, CONVT_BWD, CONV1 = 0, 1, 2, 3      # uia_conv_igemm / uia_conv_wgrad modes
 BN_SLICES = 256                            # UIA_BN_SLICES
